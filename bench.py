@@ -13,7 +13,17 @@ roofline's back-to-back launch timing (the GPU clock settles under load).
 Genotypes are synthetic (generated on the device), resident in HBM as 2-bit
 tile images before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]
+A plain run does what the headline needs and no more: setup, the warmup (the
+back-to-back session's 40 launches are the settling phase: without them the
+timed trajectory runs up to 15 % slow), the timed trajectory (HIP events
+around its launches give the roofline's kernel time), the result line.  --full
+adds what else the benchmark measures or checks: the network-joint trajectory
+through the library's communicator before the warmup (network_check) and the
+CPU baseline (cpu_baseline).  --dump-outputs DIR writes what the timed trajectory
+left (every branch's parameter vector and Metropolis status) as DIR/<name>.npy;
+the inputs are seeded, so two builds can be compared output for output.
+
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   (N > 1: one rank per GPU.  Run directly, bench.py starts the N ranks itself
    -- torch.distributed.run as a CHILD process, before anything touches the GPU
    -- and rank 0's JSON line passes through; under an outer
@@ -200,6 +210,34 @@ def network_check(ctx, dist, dist_dev, world, rank, backend, library_comm, y_net
             "timing": "HIP events on the library stream, max over ranks; warm (after one untimed trajectory)"}
 
 
+DUMP_PARAM_BYTES = 48 << 20   # --dump-outputs: parameter vectors written (the whole dump stays under 64 MB)
+
+
+def dump_outputs(ctx, dirname, rank, world, branches, status, trace):
+    """--dump-outputs: what the timed trajectory returned to its caller, as .npy files
+    (float32 / float64): the parameter vectors theta of this rank's branches after the
+    Metropolis decision (params.npy, one row per branch; of a fixed, seeded sample of
+    the branches where all of them would pass DUMP_PARAM_BYTES, their indices in
+    param_branches.npy), the per-branch HMC status (status.npy: 0 accepted, 1 rejected,
+    2 rejected early) and, network sampler, the trajectory's -H trace (trace.npy).
+    Rank r > 0 of an N-rank run writes <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 and rank else ""
+    nb = len(branches)
+    sizes = [ctx.num_params(b) for b in branches]
+    keep = max(1, min(nb, DUMP_PARAM_BYTES // (4 * max(sizes))))
+    pick = np.sort(np.random.default_rng(0).choice(nb, size=keep, replace=False)) if keep < nb else np.arange(nb)
+    params = np.zeros((len(pick), max(sizes)), np.float32)   # rows zero-padded where branches differ in size
+    for i, k in enumerate(pick):
+        params[i, :sizes[k]] = ctx.get_params(branches[k])
+    np.save(os.path.join(dirname, f"params{sfx}.npy"), params)
+    np.save(os.path.join(dirname, f"param_branches{sfx}.npy"), pick.astype(np.float64))
+    if status is not None:
+        np.save(os.path.join(dirname, f"status{sfx}.npy"), np.asarray(status, np.float32))
+    if trace is not None:
+        np.save(os.path.join(dirname, f"trace{sfx}.npy"), np.asarray(trace, np.float64))
+
+
 def launch_ranks(nproc: int) -> int:
     """`bench.py --gpus N` run directly (no WORLD_SIZE): start the N ranks as
     `torch.distributed.run` in a child process -- never exec, and nothing here
@@ -256,7 +294,14 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--step-factor", type=float, default=None,
                     help="Izmailov factor c; default 1.0 (cli.rs:99-100), 0.1 for c5, 0.02 for c3def (wide branches: acceptance > 0.6 at L = 100)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the network-joint check through the library's "
+                         "communicator (network_check) and the CPU baseline (cpu_baseline); a run without it sets "
+                         "up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed trajectory left (parameter vectors, HMC "
+                         "status; .npy, float32 / float64) into DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baseline")
     ap.add_argument("--cpu-sample-branches", type=int, default=None)   # default 96 (c3def: 4), capped at the branch count
     ap.add_argument("--cpu-sample-steps", type=int, default=None)      # default 16 (c3def: 2)
     ap.add_argument("--profile-iters", type=int, default=20)
@@ -273,7 +318,7 @@ def main():
                          "reference's own sweep order, one branch at a time against the refreshed residual "
                          "(bann_net_train, Net::train net.rs:201-358), one GPU")
     ap.add_argument("--no-network-check", action="store_true",
-                    help="skip the untimed network-joint trajectory through the library's RCCL communicator "
+                    help="--full: skip the untimed network-joint trajectory through the library's RCCL communicator "
                          "(a 1-rank one at N = 1) that runs before the warmup and is reported in the line "
                          "(network_check)")
     ap.add_argument("--network-step-rule", default="common_mode", choices=["common_mode", "adaptive", "off"],
@@ -422,7 +467,7 @@ def main():
     branches = list(range(nb))
     y_net = (noise + fsum).astype(np.float32)
 
-    net, seen = None, [0.0]
+    net, seen, last = None, [0.0], {}   # last: what the latest trajectory returned beside its acceptance count
     if args.sampler == "sequential":
         if world > 1:
             raise SystemExit("--sampler sequential is the single-device driver (Net::train)")
@@ -454,20 +499,22 @@ def main():
                                      step_factor=args.step_factor, seed=seed)
             if os.environ.get("BANN_BENCH_TRACE"):   # diagnostics: the network -H trace on stderr
                 log(json.dumps({"seed": seed, "status": int(r["status"]), "trace": [float(v) for v in r["trace"]]}))
+            last.update(status=[r["status"]], trace=r["trace"])
             return float(r["status"] == 0) * nb
         ctx.leapfrog_begin(branches, L, 10.0, "izmailov", args.step_factor, seed=seed)
         ctx.leapfrog_steps(L)
         status, acc = ctx.leapfrog_end()
+        last.update(status=status)
         return acc
 
-    # C4's collective, checked before anything is timed and reported INSIDE the
+    # --full: C4's collective, checked before anything is timed and reported INSIDE the
     # line: one network-joint trajectory through the library's communicator (RCCL
     # over xGMI at N > 1: the per-step all-reduce of the summed branch outputs),
     # from the generating state (y = sum_b f_b + noise), at the network sampler's
     # factor for its L.  A stalled collective ends the run with a non-zero exit
     # (watchdog), an error likewise; the line is never printed without it.
     netcheck = None
-    if args.sampler == "branch" and not args.no_network_check:
+    if args.full and args.sampler == "branch" and not args.no_network_check:
         import threading
         wd = threading.Timer(180.0, lambda: (log(f"network_check: rank {rank}: collective stalled"), os._exit(3)))
         wd.daemon = True
@@ -560,6 +607,8 @@ def main():
         acc_all, nb_all = float(ta[0]), float(ta[1])
     else:
         acc_all, nb_all = float(acc), float(nb)
+    if args.dump_outputs:   # before any further trajectory moves the chain
+        dump_outputs(ctx, args.dump_outputs, rank, world, branches, last.get("status"), last.get("trace"))
     # acceptance over more (untimed) trajectories: the network sampler takes ONE
     # Metropolis decision per trajectory, so a single trajectory says 0 or 1
     n_extra = args.accept_trajectories if args.accept_trajectories is not None else (
@@ -618,7 +667,7 @@ def main():
             break
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sample_b = min(args.cpu_sample_branches, B_total)
         c = cpu_baseline(n, m_b, widths, sample_b, args.cpu_sample_steps)
         if c is not None:

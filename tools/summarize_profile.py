@@ -21,7 +21,7 @@ shutil.copy(stats, os.path.join(prof, f"{tag}_kernel_stats.csv"))
 trace = list(csv.DictReader(open(find("trace", "*kernel_trace.csv"))))
 bench = json.loads(open(os.path.join(out, "bench_trace.json")).read().strip().splitlines()[-1])
 
-# the timed trajectory: bench.py runs the network check's two trajectories (when the line
+# the timed trajectory: bench.py --full runs the network check's two trajectories (when the line
 # carries network_check: an untimed one, then the timed one), the warmup trajectory, then the back-to-back measurement
 # session (a 2-step leapfrog session), then the timed trajectory; each starts with
 # one k_step_sizes launch (traj_prepare)
@@ -114,7 +114,7 @@ if mf:  # MFMA utilisation pass: per-counter medians over the full-branch-set gr
 json.dump(pmc, open(os.path.join(prof, f"{tag}_pmc.json"), "w"), indent=1)
 
 with open(os.path.join(prof, f"{tag}_summary.md"), "w") as f:
-    f.write(f"# Profile {tag}: `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline "
+    f.write(f"# Profile {tag}: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline "
             f"{' '.join(sys.argv[3:])}`\n\n")
     f.write(f"workload: {bench['config']['workload']}\n\n")
     f.write(f"bench line under the profiler: value {bench['value']:.2f} {bench['unit']}, "
