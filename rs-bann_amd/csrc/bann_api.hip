@@ -243,9 +243,9 @@ int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool
       key.full = d.nchunks == 8;
     } else if (d.fused == 3) {  // fxl: (L, act, chunks per wave, waves, every wave full)
       key.L = h.L;
-      key.cpw = fxl_cpw(d.nchunks);
+      key.cpw = fxl_cpw(d.nchunks, ctx->opt.fxl_cpw);
       key.nw = (d.nchunks + key.cpw - 1) / key.cpw;
-      key.head = ctx->fxl_head ? 1 : 0;
+      key.head = ctx->opt.fxl_head ? 1 : 0;
       key.full = d.nchunks == key.cpw * key.nw;
     } else if (d.fused == 2) {  // wx: (act, marker chunks: the plane kernel is compiled per chunk count)
       key.nw = d.nchunks;
@@ -287,7 +287,7 @@ int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool
   }
   {  // the fused update (kernels_fx.hip tail): fx branches only, the small update, one round of items
     int64_t items = 0;
-    bool ok = p.gx.empty() && ctx->d_upd_cnt != nullptr && ctx->fuse_update_mode > 0;
+    bool ok = p.gx.empty() && ctx->d_upd_cnt != nullptr && ctx->opt.fuse_update;
     bool single = true;  // every branch one split: its one workgroup updates it
     for (const auto& g : p.groups) {
       ok = ok && g.kind == 1;
@@ -331,7 +331,7 @@ int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool
         int64_t tot = 0;
         p.gx_pre.push_back(0);
         for (size_t k = i; k < j; ++k) {
-          tot += gx_tiles(ctx->br[p.gx[k]].dev, ph.ph, ph.l, ctx->nfrag);
+          tot += gx_tiles(ctx->br[p.gx[k]].dev, ph.ph, ph.l, ctx->nfrag, ctx->opt.gx_exact);
           if (tot >= (1ll << 30)) return fail(ctx, BANN_E_SHAPE, "gx phase has too many tiles for one launch");
           p.gx_pre.push_back((int32_t)tot);
         }
@@ -399,6 +399,10 @@ int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool
   return BANN_OK;
 }
 
+// launch_fused_grad_wx's mode: bf16 MFMA when opted in, else the exact-f32 MFMA (BANN_WX_EXACT=1) or the
+// f32-accurate bf16 planes; bann_finalize sized the wx splits for the same choice
+static int wx_mode(const bann_ctx* ctx) { return ctx->wide_bf16 ? 1 : (ctx->opt.wx_exact ? 0 : 2); }
+
 // gradient (partials) of every branch in the plan at the current theta.
 // write_pred: 0 = no predictions (the layered path writes them anyway), 1 = the
 // predictions f_b(theta) into pred, 2 = into pred0 (a trajectory's start: the
@@ -415,7 +419,7 @@ int run_grad(bann_ctx* ctx, const Plan& p, int write_pred, int upd_mode, int upd
   for (const auto& g : p.groups) {
     const int32_t ni = (int32_t)g.items.size();
     if (g.kind == 2)
-      launch_fused_grad_wx(s, g.d_items, ni, g.act, ctx->wide_bf16 ? 1 : (wx_exact() ? 0 : 2), g.nw, wp, ctx->stream);
+      launch_fused_grad_wx(s, g.d_items, ni, g.act, wx_mode(ctx), g.nw, wp, ctx->stream);
     else if (g.kind == 3)
       launch_fused_grad_fxl(s, g.d_items, ni, g.L, g.act, g.nw, g.cpw, g.full, wp, g.head, ctx->stream);
     else
@@ -428,9 +432,9 @@ int run_grad(bann_ctx* ctx, const Plan& p, int write_pred, int upd_mode, int upd
     launch_gx_prep(s, bl, g.count, ctx->stream);
     for (const auto& ph : g.phases) {
       if (ph.ph == GX_HEAD)
-        launch_gx_head(s, bl, g.count, g.max_splits, ctx->stream);
+        launch_gx_head(s, bl, g.count, g.max_splits, ctx->opt.gx_exact, ctx->stream);
       else
-        launch_gx_gemm(s, ph.ph, ph.l, bl, p.d_gxpre + ph.pre_off, g.count, ph.total, ctx->stream);
+        launch_gx_gemm(s, ph.ph, ph.l, bl, p.d_gxpre + ph.pre_off, g.count, ph.total, ctx->opt.gx_exact, ctx->stream);
     }
   }
   CK(hipGetLastError());
@@ -446,11 +450,12 @@ int run_forward(bann_ctx* ctx, const Plan& p) {
   for (const auto& g : p.groups) {
     const int32_t ni = (int32_t)g.items.size();
     if (g.kind == 2)
-      launch_fused_grad_wx(s, g.d_items, ni, g.act, ctx->wide_bf16 ? 1 : (wx_exact() ? 0 : 2), g.nw, 1, ctx->stream);
+      launch_fused_grad_wx(s, g.d_items, ni, g.act, wx_mode(ctx), g.nw, 1, ctx->stream);
     else if (g.kind == 3)
       launch_fused_grad_fxl(s, g.d_items, ni, g.L, g.act, g.nw, g.cpw, g.full, 1, g.head, ctx->stream);
     else if (g.fi)
-      launch_forward_fi(s, g.d_items, ni, g.tiles, g.L, g.act, g.max_seg, ctx->cus, ctx->stream);
+      launch_forward_fi(s, g.d_items, ni, g.tiles, g.L, g.act, g.max_seg, ctx->cus, ctx->opt.fi_waves_per_simd,
+                        ctx->stream);
     else
       launch_forward_fx(s, g.d_items, ni, g.L, g.act, g.full, ctx->stream);
   }
@@ -459,10 +464,10 @@ int run_forward(bann_ctx* ctx, const Plan& p) {
     launch_gx_prep(s, bl, g.count, ctx->stream);
     for (const auto& ph : g.phases) {
       if (ph.ph == GX_HEAD) {
-        launch_gx_head(s, bl, g.count, g.max_splits, ctx->stream);
+        launch_gx_head(s, bl, g.count, g.max_splits, ctx->opt.gx_exact, ctx->stream);
         break;  // the head writes the predictions; the backward phases are not needed
       }
-      launch_gx_gemm(s, ph.ph, ph.l, bl, p.d_gxpre + ph.pre_off, g.count, ph.total, ctx->stream);
+      launch_gx_gemm(s, ph.ph, ph.l, bl, p.d_gxpre + ph.pre_off, g.count, ph.total, ctx->opt.gx_exact, ctx->stream);
     }
   }
   CK(hipGetLastError());
@@ -504,12 +509,9 @@ extern "C" int bann_ctx_create(int device, bann_ctx** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return BANN_E_HIP;
   if (device < 0 || device >= ndev) return BANN_E_ARG;
-  bann_ctx* ctx = new bann_ctx();
+  bann_ctx* ctx = new bann_ctx();  // reads every BANN_* switch, once (bann_ctx::opt)
   ctx->device = device;
-  if (const char* e = getenv("BANN_HMC_GRAPH")) ctx->graph_replay = atoi(e) != 0;
-  if (const char* e = getenv("BANN_FXL_HEAD")) ctx->fxl_head = atoi(e) != 0;
-  if (const char* e = getenv("BANN_NET_GSUM")) ctx->net_gsum = atoi(e) != 0;
-  if (const char* e = getenv("BANN_FUSE_UPDATE")) ctx->fuse_update_mode = atoi(e) != 0 ? 1 : 0;
+  ctx->graph_replay = ctx->opt.hmc_graph > 0;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
     delete ctx;
     return BANN_E_HIP;
@@ -815,12 +817,11 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
       d.fused = 2;
     if (d.fused) total_frags += ctx->nfrag;
   }
-  int64_t target_items = 1024;  // wx (and fx with BANN_TARGET_ITEMS / BANN_MIN_FRAGS): ~target work items
-  if (const char* e = getenv("BANN_TARGET_ITEMS")) target_items = std::max<int64_t>(1, atoll(e));
-  int64_t min_frags = 64;  // >= 16 tiles per work item amortises the per-item prologue/epilogue
-  if (const char* e = getenv("BANN_MIN_FRAGS")) min_frags = std::max<int64_t>(1, atoll(e));
+  const EnvOptions& opt = ctx->opt;
+  // wx (and fx with BANN_TARGET_ITEMS / BANN_MIN_FRAGS): ~target_items work items (default 1024) of at
+  // least min_frags fragments (default 64: >= 16 tiles per work item amortises the per-item prologue/epilogue)
   const int64_t frags_per_item =
-      std::max<int64_t>(min_frags, (total_frags + target_items - 1) / std::max<int64_t>(1, target_items));
+      std::max<int64_t>(opt.min_frags, (total_frags + opt.target_items - 1) / opt.target_items);
   const int64_t ntile = (ctx->nfrag + BANN_TILE_FRAGS - 1) / BANN_TILE_FRAGS;
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0)
@@ -847,10 +848,9 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
     }
     return best_sp;
   };
-  const bool env_split = getenv("BANN_TARGET_ITEMS") || getenv("BANN_MIN_FRAGS");
   int64_t nfx = 0, nfxl[2][9] = {};  // fxl branches by (chunks per wave 4?, waves)
-  auto fxl_key = [](int nch, int& c4, int& nw) {
-    const int cpw = fxl_cpw(nch);
+  auto fxl_key = [&](int nch, int& c4, int& nw) {
+    const int cpw = fxl_cpw(nch, opt.fxl_cpw);
     c4 = cpw == 4;
     nw = (nch + cpw - 1) / cpw;
   };
@@ -867,7 +867,7 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   for (auto& h : ctx->br) nwx += h.dev.fused == 2;
   // wx: 4 two-wave workgroups per CU, a tile at a time (exact f32 MFMA); wx3: 2
   // four-wave workgroups per CU, two tiles at a time
-  const int32_t wx_splits = wx_exact() ? best_splits(nwx, 4 * (int64_t)cus, 1) : best_splits(nwx, 2 * (int64_t)cus, 2);
+  const int32_t wx_splits = opt.wx_exact ? best_splits(nwx, 4 * (int64_t)cus, 1) : best_splits(nwx, 2 * (int64_t)cus, 2);
   int32_t fxl_splits[2][9] = {};
   for (int c4 = 0; c4 < 2; ++c4)
     for (int nw = 1; nw <= 8; ++nw) {  // fxl: all waves of a workgroup on one tile; LDS- and VGPR-limited residency
@@ -880,7 +880,7 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   // the LDS forward (k_forward_fx): inside the network trajectory, interleaved with the
   // gradient launches, it measured faster (2.573 vs 2.660 ms per step, r4c/r4d), and it
   // needs no second 2-bit image
-  const bool fi_on = getenv("BANN_FWD_FI") && atoi(getenv("BANN_FWD_FI")) != 0;
+  const bool fi_on = opt.fwd_fi;
   int64_t xi_off = 0;
   int64_t x2_off = 0, dig_off = 0, p_off = 0, mk_off = 0, part_off = 0, scr_off = 0, items = 0;
   // gx scratch groups: branches in index order until the budget (BANN_GX_SCRATCH_MB,
@@ -894,7 +894,7 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
     if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 0)
       gx_budget = std::max<int64_t>(gx_budget, std::min<int64_t>((int64_t)(fr / 4) / 4, 65536ll << 18));
   }
-  if (const char* e = getenv("BANN_GX_SCRATCH_MB")) gx_budget = std::max<int64_t>(1, atoll(e)) << 18;
+  if (opt.gx_scratch_mb > 0) gx_budget = opt.gx_scratch_mb << 18;
   int64_t gx_cur = 0, n_gx = 0;
   int32_t gx_ngroups = 0;
   int32_t max_splits = 1;
@@ -930,7 +930,7 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
     // gx: row splits of ~64 tiles (4096 individuals) for the K = n gradient GEMMs
     d.nsplits = d.fused ? (int32_t)std::max<int64_t>(1, (ctx->nfrag + frags_per_item - 1) / frags_per_item)
                         : (int32_t)((ntile + 63) / 64);
-    if (d.fused == 1 && !env_split) d.nsplits = fx_splits;
+    if (d.fused == 1 && !opt.env_split) d.nsplits = fx_splits;
     if (d.fused == 3) {
       int c4, nw;
       fxl_key(d.nchunks, c4, nw);
@@ -996,8 +996,7 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   ctx->max_splits = max_splits;
   // solo mode (build_plan): ~one tile per wave for a branch alone on the GPU
   // (BANN_SOLO_TPW: more tiles per wave, fewer slabs to fold)
-  int64_t solo_tpw = 1;
-  if (const char* e = getenv("BANN_SOLO_TPW")) solo_tpw = std::max(1, atoi(e));
+  const int64_t solo_tpw = opt.solo_tpw;
   int64_t max_p_fused = 0;
   for (auto& h : ctx->br) {
     const BranchDev& d = h.dev;
@@ -1008,8 +1007,7 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
     h.solo_items = (int32_t)std::max<int64_t>(d.nsplits,
                                               std::min<int64_t>(2 * cus, (ntile + per_item - 1) / per_item));
   }
-  ctx->solo_threshold = cus;
-  if (const char* e = getenv("BANN_SOLO")) ctx->solo_threshold = atoi(e) ? cus : 0;  // 0: never re-split
+  ctx->solo_threshold = opt.solo ? cus : 0;  // BANN_SOLO=0: never re-split
   ctx->solo_rss_cap = 8ll * cus;
   ctx->solo_part_cap = ctx->solo_rss_cap * max_p_fused;
   ctx->part_total = part_off;
@@ -1158,7 +1156,7 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   CK(dalloc(&ctx->d_br, nb));
   CK(hipMemcpyAsync(ctx->d_br, descs.data(), nb * sizeof(BranchDev), hipMemcpyHostToDevice, ctx->stream));
   CK(hipMemcpyAsync(ctx->d_eprec, eprec.data(), nb * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  if (getenv("BANN_STAMPS")) {
+  if (opt.stamps) {
     CK(hipMalloc((void**)&ctx->d_dbg, 16 * sizeof(unsigned long long)));
     CK(hipMemsetAsync(ctx->d_dbg, 0, 16 * sizeof(unsigned long long), ctx->stream));
   }
@@ -1676,7 +1674,9 @@ static int hmc_outputs(bann_ctx* ctx, const int32_t* branches, int32_t nb, int32
 // GPU, paces it.  The sequence of a plan shape is captured once into a HIP
 // graph and replayed; the plan's device arrays live in the context's scratch
 // buffers (fixed addresses), so one graph serves every branch of the same shape.
-// The key holds everything the captured kernel arguments depend on.
+// The key holds everything the captured kernel arguments depend on and that can change
+// within a context: graphs are cached per context and the BANN_* switches (bann_ctx::opt)
+// are fixed for its life, so none of them is a field; wide_bf16 is one, being settable.
 static std::string traj_graph_key(const bann_ctx* ctx, const Plan& p, int32_t L) {
   std::string k;
   auto put = [&](int64_t v) { k.append(reinterpret_cast<const char*>(&v), sizeof(v)); };

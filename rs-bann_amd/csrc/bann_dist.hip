@@ -237,7 +237,7 @@ int net_buffers_init(bann_ctx* ctx) {
     const BranchHost& last = ctx->br.back();
     CK(dalloc(&ctx->d_cm_scale, last.dev.p_off + last.P));
   }
-  if (!ctx->d_gsum && ctx->net_gsum) {  // one row per (at least) 8 fx branches of 8 chunks and one (L, act)
+  if (!ctx->d_gsum && ctx->opt.net_gsum) {  // one row per (at least) 8 fx branches of 8 chunks and one (L, act)
     std::vector<std::pair<int64_t, int32_t>> cls;  // ((L, act), count)
     for (const auto& h : ctx->br)
       if (h.dev.fused == 1 && h.dev.nchunks == 8) {
@@ -289,8 +289,7 @@ int build_net_groups(bann_ctx* ctx, Plan& p) {
   const int64_t ntile = ((int64_t)ctx->nfrag + BANN_TILE_FRAGS - 1) / BANN_TILE_FRAGS;
   const int64_t tmax = forward_gsum_max_tiles();
   const int64_t slots = ctx->cus;
-  int force_r = 0;
-  if (const char* e = getenv("BANN_NET_GSUM_R")) force_r = std::max(1, atoi(e));
+  const int force_r = ctx->opt.net_gsum_r;
   int32_t row = 0;
   for (auto& g : p.groups) {
     std::vector<int32_t> brs;
@@ -471,8 +470,7 @@ extern "C" int bann_network_hmc_step(bann_ctx* ctx, const float* y, float bias, 
   // fx-only plans: the gradient kernel reads e itself (DevState::nete), no per-branch targets
   bool fx_only = p.gx.empty();
   for (const auto& g : p.groups) fx_only = fx_only && g.kind == 1;
-  if (const char* e = getenv("BANN_NET_ERR"))  // 0: per-branch targets for every kind (diagnostics)
-    fx_only = fx_only && atoi(e) != 0;
+  fx_only = fx_only && ctx->opt.net_err;  // BANN_NET_ERR=0: per-branch targets for every kind (diagnostics)
   ctx->st.nete = fx_only ? ctx->d_netsum : nullptr;
   // group sums (k_forward_gsum): every step's forward but the last writes one row per group of
   // four branches instead of every branch's outputs -- the step needs only their sum, and the

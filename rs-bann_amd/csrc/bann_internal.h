@@ -180,11 +180,14 @@ void launch_gather_stats(const float* mu, const float* sigma, const int32_t* snp
 
 // gx: the layered MFMA path (kernels_gx.hip)
 enum { GX_FWD0 = 0, GX_FWD = 1, GX_BWD = 2, GX_GRAD = 3, GX_GRAD0 = 4, GX_HEAD = 5 };
-int64_t gx_tiles(const BranchDev& d, int ph, int l, int32_t nfrag);
+// exact (EnvOptions::gx_exact): every phase on the exact-f32 MFMA path with 64 x 64 tiles and the eager
+// head; else the bf16-plane kernels, their tile shapes and the lazy head.  One value for gx_tiles' counts
+// and every launch over them
+int64_t gx_tiles(const BranchDev& d, int ph, int l, int32_t nfrag, bool exact);
 void launch_gx_prep(const DevState& st, const int32_t* blist, int nb, hipStream_t s);
-void launch_gx_head(const DevState& st, const int32_t* blist, int nb, int max_splits, hipStream_t s);
+void launch_gx_head(const DevState& st, const int32_t* blist, int nb, int max_splits, bool exact, hipStream_t s);
 void launch_gx_gemm(const DevState& st, int ph, int l, const int32_t* blist, const int32_t* prefix, int nb,
-                    int total, hipStream_t s);
+                    int total, bool exact, hipStream_t s);
 #define GX_HEAD_MAXW 4096   // widest summary layer of a gx branch
 void launch_fold_solo(const DevState& st, const FoldJob* jobs, int32_t njobs, int32_t max_p, hipStream_t s);
 void launch_update(const DevState& st, const int32_t* branches, int32_t nb, int32_t mode, int32_t step,
@@ -232,7 +235,6 @@ void launch_uniforms(const DevState& st, const int32_t* branches, int32_t nb, ui
 // mode 0 exact f32 MFMA, 1 bf16 MFMA, 2 f32-accurate bf16 planes (kernels_wx.hip)
 void launch_fused_grad_wx(const DevState& st, const GradItem* items, int32_t nitems, int32_t act, int mode,
                           int nch, int write_pred, hipStream_t s);
-bool wx_exact();
 // upd_cnt != null: the fused leapfrog update (mode, step) in the tail -- the last workgroup of
 // each branch updates it (update_core.h); upd_cnt = one zeroed arrival counter per branch
 void launch_fused_grad_fx(const DevState& st, const GradItem* items, int32_t nitems, int32_t L, int32_t act,
@@ -243,13 +245,13 @@ void launch_forward_fx(const DevState& st, const GradItem* items, int32_t nitems
                        hipStream_t s);
 // forward-only fx pass over the individual-major fi images (kernels_fi.hip)
 void launch_forward_fi(const DevState& st, const GradItem* items, int32_t nitems, int64_t total_tiles, int32_t L,
-                       int32_t act, int32_t max_seg, int32_t cus, hipStream_t s);
+                       int32_t act, int32_t max_seg, int32_t cus, int32_t waves_per_simd, hipStream_t s);
 void launch_pack_fi(const uint8_t* raw, int64_t rowb, const PackJob* jobs, int32_t njobs, const int32_t* idx,
                     int64_t ntile, uint8_t* dst, hipStream_t s);
 void launch_fused_grad_fxl(const DevState& st, const GradItem* items, int32_t nitems, int32_t L, int32_t act,
                            int32_t nw, int32_t cpw, int full, int write_pred, int head, hipStream_t s);
 int fxl_lds_bytes(int nw, int nl, int cpw);
-int fxl_cpw(int nchunks);  // marker chunks per fxl wave: 4 up to 32 chunks, else 8
+int fxl_cpw(int nchunks, int force);  // marker chunks per fxl wave: 4 up to 32 chunks, else 8 (force = 8: always 8)
 void launch_step_sizes(const DevState& st, const double* base, const int32_t* branches, int32_t nb, int32_t max_p,
                        int izmailov, float c, int32_t L, hipStream_t s);
 void launch_restore_pred(const DevState& st, const int32_t* branches, int32_t nb, hipStream_t s);

@@ -1049,7 +1049,10 @@ int train_record(bann_net* t, int chain_ix, const bann_mcmc_cfg* cfg, const std:
 namespace {
 // the driver's one-branch trajectories are launch-latency-bound: replay each as one
 // captured HIP graph (bann_set_graph_replay) unless BANN_HMC_GRAPH=0; the
-// context's previous setting is restored after training
+// context's previous setting is restored after training.  This is the library's one
+// environment read outside read_env_options (env_options.h): this file is built without
+// HIP and reaches the context only through the C ABI, so it reads the variable itself, at
+// bann_net_train's entry
 struct GraphReplayScope {
   bann_ctx* ctx;
   int32_t prev;

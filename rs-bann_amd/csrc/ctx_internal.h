@@ -9,6 +9,7 @@
 
 #include "../../include/bann.h"
 #include "bann_internal.h"
+#include "env_options.h"
 
 struct BranchHost {
   std::vector<int32_t> snp_idx;
@@ -28,7 +29,7 @@ struct LaunchGroup {
   int32_t kind = 0;  // BranchDev::fused of its branches: 1 fx, 3 fxl, 2 wx
   int32_t L = 0, act = 0, nw = 1, full = 0;
   int32_t cpw = 8;      // fxl: marker chunks per wave (fxl_cpw)
-  int32_t head = 0;     // fxl: the head-wave kernel fxh where its shape allows (bann_ctx::fxl_head)
+  int32_t head = 0;     // fxl: the head-wave kernel fxh where its shape allows (EnvOptions::fxl_head)
   int64_t tiles = 0;    // fx: the items' 64-individual tiles (the fi forward's index space, GradItem::tile0)
   int32_t max_seg = 1;  // fx: the largest 256-marker segment count of its branches
   bool fi = false;      // fx: every branch has an individual-major fi image (kernels_fi.hip)
@@ -88,8 +89,9 @@ struct bann_ctx {
   std::vector<BranchHost> br;
   bool finalized = false;
   bool fused_enabled = true;
-  bool wide_bf16 = false;
-  bool fxl_head = true;    // fxl groups of 17..32 chunks on the head-wave kernel (BANN_FXL_HEAD=0 at creation: off)  // wx kernel: hidden GEMMs on bf16 MFMA (opt-in, reduced precision)
+  bool wide_bf16 = false;  // wx kernel: hidden GEMMs on bf16 MFMA (opt-in, reduced precision)
+  // the BANN_* switches, read once as bann_ctx_create constructs the context and fixed for its life
+  const EnvOptions opt = read_env_options();
   int32_t nfrag = 0, max_splits = 1;
   int64_t packed_bytes = 0, total_p = 0;
   // device buffers
@@ -99,12 +101,6 @@ struct bann_ctx {
   int64_t xi_bytes = 0;
   int32_t cus = 256;
   int32_t* d_upd_cnt = nullptr;  // per-branch arrival counters of the fused update (zero between launches)
-  // the update in the gradient launch's tail (BANN_FUSE_UPDATE=1; same bits either way):
-  // one-split plans (the branch's one workgroup), one-round multi-split plans and solo
-  // plans (the last arriving workgroup; solo: it folds the branch's slabs first).  Off
-  // by default: measured slower everywhere (r4c: C3 747.7 vs 752.9 steps/s, N = 8 shard
-  // 4 269 vs 4 531, sequential driver 6.5 vs 21.9 -- one workgroup adding 49 slabs)
-  int fuse_update_mode = 0;
   uint8_t* d_dig = nullptr;
   FusedConst* d_fc = nullptr;
   float *d_mub = nullptr, *d_sigb = nullptr;
@@ -148,7 +144,6 @@ struct bann_ctx {
   void* ar_user = nullptr;
   float* d_gsum = nullptr;     // network mode: per-group output sums of the fx branches (gsum_cap rows of n)
   int32_t gsum_cap = 0;
-  bool net_gsum = true;        // BANN_NET_GSUM=0 at creation: per-branch output rows in every step (A/B)
   float* d_netsum = nullptr;   // network mode: n-vector sum of the local branch outputs, then the error e
   float* d_nety = nullptr;     // network mode: the targets y
   double* d_netrss = nullptr;  // network mode: global rss per leapfrog step (netrss_cap entries)
@@ -206,7 +201,9 @@ struct bann_ctx {
   };
   std::vector<Rec> rec;  // indexed by branch
   // captured launch sequences of bann_hmc_step, keyed by plan shape, L and the by-value state
-  bool graph_replay = false;  // BANN_HMC_GRAPH=1: replay captured graphs (+5 % sequential; rocprofv3 crashes on them)
+  // replay captured graphs (+5 % sequential; rocprofv3 crashes on them): starts as BANN_HMC_GRAPH=1
+  // (EnvOptions::hmc_graph), then bann_set_graph_replay's
+  bool graph_replay = false;
   std::vector<std::pair<std::string, hipGraphExec_t>> graphs;
   // leapfrog session
   Plan lf;

@@ -279,9 +279,9 @@ static void launch_fi_nl(const DevState& st, const GradItem* items, int32_t nite
 // items: one fx launch group (every branch has an fi image), tile0 = the prefix
 // of the items' tile counts; max_seg: the group's largest segment count
 void launch_forward_fi(const DevState& st, const GradItem* items, int32_t nitems, int64_t total_tiles, int32_t L,
-                       int32_t act, int32_t max_seg, int32_t cus, hipStream_t s) {
+                       int32_t act, int32_t max_seg, int32_t cus, int32_t waves_per_simd, hipStream_t s) {
   if (nitems <= 0 || total_tiles <= 0) return;
-  const int64_t waves = (int64_t)cus * 4 * (int64_t)(getenv("BANN_FI_WAVES_PER_SIMD") ? atoi(getenv("BANN_FI_WAVES_PER_SIMD")) : 3);
+  const int64_t waves = (int64_t)cus * 4 * (int64_t)waves_per_simd;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(waves, total_tiles) / FI_WAVES);
   switch (L * 2 + (max_seg > 1 ? 1 : 0)) {
     case 4: launch_fi_nl<2, 1>(st, items, nitems, act, grid, s); break;

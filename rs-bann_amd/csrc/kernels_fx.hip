@@ -71,16 +71,13 @@
 #ifndef FX_STAMPS
 #define FX_STAMPS 0
 #endif
-// the backward's genotype-window prefetch depth and its per-window scheduling barrier (round 6,
+// the backward's genotype-window prefetch depth, without a scheduling barrier per window (round 6,
 // kbench and C3 line A/B on one box: PD 8 -> 12 without the barrier, fx 1.181 / 1.190 -> 1.173 /
 // 1.169 ms, 780.7 / 774.5 -> 785.4 / 787.1 steps/s; a barrier-free PD 8: 1.175 / 1.177; measured and
 // not kept: the forward at priority 0, the head at 2, the backward at 1, the forward three chunks
 // ahead, PD 4 or 16, no barrier per forward chunk -- tools/gpu_kab.sh, profiles/r06_fx_knobs.txt)
 #ifndef FXT_PD
 #define FXT_PD 12  // backward: genotype window reads this many windows ahead
-#endif
-#ifndef FXT_SBB
-#define FXT_SBB 0  // a scheduling barrier after each backward window (1: the round-5 schedule)
 #endif
 #ifndef FX_ABL
 #define FX_ABL 0
@@ -592,7 +589,6 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
         if (u + PD < 32 && (NCH != 0 || u + PD < 4 * nch))  // slot of window u, consumed two iterations ago
           wq[u % PD] = *reinterpret_cast<const uint32_t*>(xs + 256 * (u + PD) + (((u + PD) & 1) ? boo : boe));
         acc[u] = FX_MFMA(A, Bv, acc[u]);
-        if (FXT_SBB) __builtin_amdgcn_sched_barrier(0);
       }
     }
     FX_STAMP(4);
@@ -787,25 +783,9 @@ void launch_fused_grad_fx(const DevState& st, const GradItem* items, int32_t nit
 // stream runs two tiles ahead in the wave's two slots, the refill of a slot is
 // issued once the forward has read it (the head's prediction store first, so
 // the counted wait at the top never waits on a piece younger than the tile).
+// Variants measured against this forward and not kept: DESIGN.md section 9.
 // ===========================================================================
-#ifndef FWD_NU
-#define FWD_NU 3  // 8-chunk forward: half-tile units per wave (0: whole-tile slots, the A/B variant)
-#endif
-#ifndef FWD_ABL
-#define FWD_ABL 0  // timing ablations of the ring forward (tools only; results wrong): 1 no MFMA, 2 no head, 4 no stream,
-                  // 8 predictions stored by wave 0 only
-#endif
-#ifndef FWD_PB
-#define FWD_PB 8  // ring forward: tiles per prediction write burst (1: one store per tile, counted in the waits:
-                  // kbench 1.134 vs 1.173 ms, but 1.203 vs 1.181 ms inside the network trajectory)
-#endif
-#ifndef FWD_PBC
-#define FWD_PBC 0  // PB > 1: count the bursts' stores in the waits too
-#endif
-#ifndef FWD_NS
-#define FWD_NS 2  // tile slots per wave: the stream runs FWD_NS tiles ahead (2: two workgroups per CU;
-                  // round 5, network line A/B: 379.6 / 381.2 vs 376.0 / 377.2 steps/s with 4, 376.6 / 378.2 with 3)
-#endif
+constexpr int FWD_NU = 3;  // 8-chunk tiles: half-tile units per wave (tiles of fewer chunks: 0, whole-tile slots)
 // all but the youngest k (0 .. 31) vector-memory operations of this wave are complete
 __device__ __forceinline__ void vm_wait_n(int k) {
 #define VMW(i) \
@@ -822,11 +802,11 @@ __device__ __forceinline__ void vm_wait_n(int k) {
 // NU > 0 (8-chunk tiles): the half-tile ring, NU units of 4 KiB per wave and the W0 digits in
 // registers (no LDS copy), so that 4 NU KiB per wave set the workgroups per CU
 template <int NL, int ACT, int NCH, int NU>
-__global__ void __launch_bounds__(64 * FX_WAVES, NU > 0 ? 2 : (FWD_NS <= 2 ? 2 : 1))
+__global__ void __launch_bounds__(64 * FX_WAVES, 2)
     k_forward_fx(DevState st, const GradItem* __restrict__ items) {
   constexpr int NH = NL - 1;
   constexpr int NW = FX_WAVES;
-  constexpr int NS = FWD_NS;
+  constexpr int NS = 2;  // whole-tile ring (NU == 0): tile slots per wave, the stream runs NS tiles ahead
   static_assert(NU == 0 || NCH == 8, "the half-tile ring needs 8-chunk tiles");
   __shared__ __attribute__((aligned(16))) char s_x[NW][NU > 0 ? 1 : NS][NU > 0 ? NU * 4096 : FX_SLOT];
   __shared__ __attribute__((aligned(16))) char s_w0[NU > 0 ? 16 : 8 * 1024];
@@ -941,14 +921,13 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NU > 0 ? 2 : (FWD_NS <= 2 ? 2 :
     // run of the item's tiles and writes its predictions PB tiles at a time (PB x 256 bytes,
     // back to back): single 256-byte stores between the stream's reads cost the launch a
     // fifth of its time (profiles/r05_fwd_store_ablation.md).
-    constexpr int PB = FWD_PB;
+    constexpr int PB = 8;
     char* const xw = &s_x[wave][0][0];
     const int q = (te - tb + NW - 1) / NW;
     const int tw0 = tb + wave * q;
     const int nt = te - tw0 < 0 ? 0 : (te - tw0 < q ? te - tw0 : q);
     const int nu = 2 * nt;
     auto issue_unit = [&](int u) {
-      if constexpr (FWD_ABL & 4) return;
       const int64_t tt = tw0 + (u >> 1);
       char* dst = xw + (u % NU) * 4096;
 #pragma unroll
@@ -965,28 +944,17 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NU > 0 ? 2 : (FWD_NS <= 2 ? 2 :
       for (int j = 0; j < PB; ++j) {
         const int k = k0 + j;
         obuf[j] = 0.f;
-        if (PB > 1 && k >= nt) break;
+        if (k >= nt) break;
         v4i facc[4] = {v4i{0, 0, 0, 0}, v4i{0, 0, 0, 0}, v4i{0, 0, 0, 0}, rowsum64};
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int u = 2 * k + h;
-          // younger than unit u: the units issued after it (through u + NU - 1, four pieces
-          // each) and, with one prediction store per tile (PB = 1), the stores of tiles kb
-          // that ended after u was issued (tile kb stores right after issuing unit
-          // 2 kb + 1 + NU): kb in [ceil((u - NU - 1) / 2), floor((u - 2) / 2)].  Vector memory
-          // operations leave vmcnt in issue order on gfx9 (loads, stores and LDS-DMA alike),
-          // so counting them is exact; a wait that left the stores out would also wait for
-          // them, i.e. for the whole ring behind a store to HBM (profiles/r05_fwd_store_ablation.md).
-          // The stores of tiles before a wave's last are full (every row < n), so each is one
-          // issued instruction.
+          // younger than unit u: the units issued after it (through u + NU - 1), four pieces each
+          // (vector memory operations leave vmcnt in issue order on gfx9).  The bursts' prediction
+          // stores are not counted, so a wait issued behind a burst also waits for its stores;
+          // counting them measured slower inside the trajectory
           const int last = u + NU - 1 < nu - 1 ? u + NU - 1 : nu - 1;
-          int younger_st = 0;
-          if constexpr ((PB == 1 || FWD_PBC) && !(FWD_ABL & 8)) {
-            const int lo = u - NU - 1 <= 0 ? 0 : (u - NU) >> 1, hi = (u - 2) >> 1;
-            if (u >= 2)  // PB > 1: the tiles that end a burst (kb % PB == PB - 1) store PB rows of 64
-              for (int kb = lo; kb <= hi; ++kb) younger_st += (PB == 1 || kb % PB == PB - 1) ? PB : 0;
-          }
-          if constexpr (!(FWD_ABL & 4)) vm_wait_n(4 * (last - u) + younger_st);
+          vm_wait_n(4 * (last - u));
           const char* xs = xw + (u % NU) * 4096;
           v4u Xq[2];
 #pragma unroll
@@ -995,11 +963,7 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NU > 0 ? 2 : (FWD_NS <= 2 ? 2 :
           for (int c = 0; c < 4; ++c) {
             const v4u Xc = Xq[c % 2];
             if (c + 2 < 4) Xq[c % 2] = (v4u)lds_tr8_pair(xs + (c + 2) * 1024 + fo0, xs + (c + 2) * 1024 + fo1);
-            if constexpr (FWD_ABL & 1) {
-              facc[c] ^= (v4i)Xc;
-            } else {
-              fx_fwd_chunk(Areg[4 * h + c], Xc, facc);
-            }
+            fx_fwd_chunk(Areg[4 * h + c], Xc, facc);
             __builtin_amdgcn_sched_barrier(0);
           }
           // every read of this unit's slot has returned (the MFMAs consumed them): refill it
@@ -1007,16 +971,12 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NU > 0 ? 2 : (FWD_NS <= 2 ? 2 :
           if (u + NU < nu) issue_unit(u + NU);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (FWD_ABL & 2) {
-          obuf[j] = (float)(facc[0].x ^ facc[1].y ^ facc[2].z ^ facc[3].w);
-        } else {
-          obuf[j] = head_out(facc);
-        }
+        obuf[j] = head_out(facc);
       }
 #pragma unroll
       for (int j = 0; j < PB; ++j) {
         const int64_t row = 64 * (int64_t)(tw0 + k0 + j) + iota;
-        if (k0 + j < nt && row < n && (!(FWD_ABL & 8) || wave == 0)) predb[row] = obuf[j];
+        if (k0 + j < nt && row < n) predb[row] = obuf[j];
       }
     }
   } else {
@@ -1343,14 +1303,6 @@ void launch_forward_gsum(const DevState& st, const NetGroupItem* items, int32_t 
 #define FXH_NSL 4   // genotype slots per compute wave
 #ifndef FXL_PD
 #define FXL_PD 8  // backward genotype-window prefetch depth
-#endif
-// fxh compute waves without the per-window / per-chunk scheduling barriers (round 6, kbench at C2,
-// three alternating reps: 0.0921 -> 0.0888 ms per launch; either alone 0.0899 / ~0.092; profiles/r06_fx_knobs.txt)
-#ifndef FXH_SBB
-#define FXH_SBB 0  // a scheduling barrier after each backward window (1: the round-5 schedule)
-#endif
-#ifndef FXH_SBF
-#define FXH_SBF 0  // a scheduling barrier after each forward chunk (1: the round-5 schedule)
 #endif
 #ifndef FXL_DPRE
 #define FXL_DPRE 31  // backward window after which the next tile's first digit loads issue (earlier: spills)
@@ -1829,8 +1781,7 @@ static void launch_fxl_nl(const DevState& st, const GradItem* items, int32_t nit
 #undef FXL_GO
 }
 
-int fxl_cpw(int nchunks) {
-  static const int force = getenv("BANN_FXL_CPW") ? atoi(getenv("BANN_FXL_CPW")) : 0;  // 8: the old scheme (A/B)
+int fxl_cpw(int nchunks, int force) {  // force = 8 (EnvOptions::fxl_cpw): the old scheme (A/B)
   return (nchunks <= 4 * FXL_MAXW && force != 8) ? 4 : 8;
 }
 
@@ -2239,7 +2190,6 @@ __global__ void __launch_bounds__(64 * (FXH_MAXC + 1), 1)
             asm volatile("" ::"v"(Bn2));
             if (refill) glds16(rsrc + (u >> 2) * 1024, xslot0 + (k % NSL) * SLOT + (u >> 2) * 1024);
           }
-          if (FXH_SBB) __builtin_amdgcn_sched_barrier(0);
         }
       }
       // ---- forward of tile p: partial Z0 over this wave's chunks -> exchange slot p % 2 ----
@@ -2257,7 +2207,6 @@ __global__ void __launch_bounds__(64 * (FXH_MAXC + 1), 1)
           v4u Xn = Xc;
           if (c + 1 < CW) Xn = (v4u)lds_tr8_pair(xs + (c + 1) * 1024 + fo0, xs + (c + 1) * 1024 + fo1);
           fx_fwd_chunk(Dres[c], Xc, facc);
-          if (FXH_SBF) __builtin_amdgcn_sched_barrier(0);
           Xc = Xn;
         }
         fx_fwd_fields(facc);
@@ -2316,6 +2265,6 @@ static void launch_fxh_nl(const DevState& st, const GradItem* items, int32_t nit
 }
 
 // the head-wave kernel for fxl groups of 4-chunk waves with >= 5 waves (17 .. 32
-// chunks); head = the context's choice (bann_ctx::fxl_head, read once at context
+// chunks); head = the context's choice (EnvOptions::fxl_head, read once at context
 // creation: BANN_FXL_HEAD=0 keeps fxl for A/B), part of the launch group and its graph key
 bool fxh_takes(int nw, int cpw, int head) { return head && cpw == 4 && nw >= 5 && nw <= 8; }

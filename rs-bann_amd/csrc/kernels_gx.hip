@@ -1476,22 +1476,17 @@ __global__ void __launch_bounds__(256) k_gx_head_red(DevState st, const int32_t*
 void launch_gx_prep(const DevState& st, const int32_t* blist, int nb, hipStream_t s) {
   if (nb > 0) hipLaunchKernelGGL(k_gx_prep, dim3(nb, GX_PREP_Y), dim3(256), 0, s, st, blist);
 }
-static bool gx_exact() {
-  const char* ex = getenv("BANN_GX_EXACT");  // 1: every phase on the exact-f32 MFMA path
-  return ex && atoi(ex) != 0;
-}
-void launch_gx_head(const DevState& st, const int32_t* blist, int nb, int max_splits, hipStream_t s) {
+void launch_gx_head(const DevState& st, const int32_t* blist, int nb, int max_splits, bool exact, hipStream_t s) {
   if (nb <= 0) return;
-  const int fuse = gx_exact() ? 0 : 1;  // the lazy head pairs with the bf16-plane BWD / GRAD (k_gx_gemm_x3)
+  const int fuse = exact ? 0 : 1;  // the lazy head pairs with the bf16-plane BWD / GRAD (k_gx_gemm_x3)
   hipLaunchKernelGGL(k_gx_head, dim3((st.nfrag + 3) / 4, nb), dim3(256), 0, s, st, blist, fuse);
   hipLaunchKernelGGL(k_gx_head_red, dim3(max_splits, nb), dim3(256), 0, s, st, blist, fuse);
 }
 void launch_gx_gemm(const DevState& st, int ph, int l, const int32_t* blist, const int32_t* prefix, int nb,
-                    int total, hipStream_t s) {
+                    int total, bool exact, hipStream_t s) {
   if (nb <= 0 || total <= 0) return;
   const int per = (total + 7) / 8;
   const dim3 g(8 * per), blk(256);
-  const bool exact = gx_exact();
   if (!exact && ph == GX_FWD0) {
     hipLaunchKernelGGL(k_gx_gemm_b3<GX_FWD0>, g, blk, 0, s, st, blist, prefix, nb, total, per);
     return;
@@ -1518,10 +1513,10 @@ void launch_gx_gemm(const DevState& st, int ph, int l, const int32_t* blist, con
 }
 
 // tiles of phase (ph, l) for one branch: the numbering of gx_dims above
-int64_t gx_tiles(const BranchDev& d, int ph, int l, int32_t nfrag) {
+int64_t gx_tiles(const BranchDev& d, int ph, int l, int32_t nfrag, bool exact) {
   const int64_t ntile = (nfrag + 3) / 4;
   auto cd = [](int64_t a) { return (a + 63) / 64; };
-  const bool x3 = !gx_exact();  // k_gx_gemm_x3's tile shapes (X3Shape), else 64 x 64
+  const bool x3 = !exact;  // k_gx_gemm_x3's tile shapes (X3Shape), else 64 x 64
   const int64_t tmf = x3 ? 32 * X3Shape<GX_FWD>::AX : 64, tnf = x3 ? 32 * X3Shape<GX_FWD>::AY : 64;
   const int64_t tmb = x3 ? 32 * X3Shape<GX_BWD>::AX : 64, tnb = x3 ? 32 * X3Shape<GX_BWD>::AY : 64;
   const int64_t tmg = x3 ? 32 * X3Shape<GX_GRAD>::AX : 64, tng = x3 ? 32 * X3Shape<GX_GRAD>::AY : 64;

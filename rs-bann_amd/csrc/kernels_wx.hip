@@ -1002,11 +1002,6 @@ __global__ void __launch_bounds__(64 * 2 * WX3_PAIRS, 2)
   if (h == 0 && lane == 0) st.rss_part[it.rss_at] = rs;
 }
 
-bool wx_exact() {
-  const char* ex = getenv("BANN_WX_EXACT");  // 1: the hidden GEMMs on the exact-f32 MFMA (k_fused_grad_wx)
-  return ex && atoi(ex) != 0;
-}
-
 template <int BF>
 static void launch_wx_bf(const DevState& st, const GradItem* items, int32_t nitems, int act, int wp, hipStream_t s) {
   const dim3 grid((unsigned)nitems), block(64 * WX_WAVES);

@@ -701,6 +701,49 @@ def test_layered_masked_layer_modes(Ctx, exact):
     ctx.close()
 
 
+def _check_switch_fixed_per_context(monkeypatch, var, make, path):
+    """`var` picks a kernel family and the work counts sized for it; a context reads it
+    once, at creation (read_env_options), so flipping it afterwards changes nothing in
+    that context: not the gradient of a fresh per-call plan, not the forward.  make():
+    a context with one problem's parameters and targets set."""
+    def evaluate(ctx):
+        grad, rss = ctx.log_density_gradient(0)
+        ctx.set_params(0, ctx.get_params(0))  # a stale prediction row: predict launches the forward
+        return grad, rss, ctx.predict(0)
+
+    def same(x, y):
+        return np.array_equal(x[0], y[0]) and x[1] == y[1] and np.array_equal(x[2], y[2])
+
+    monkeypatch.setenv(var, "1")
+    a = make()
+    assert a.kernel_path(0) == path
+    on = evaluate(a)
+    monkeypatch.delenv(var)
+    assert same(evaluate(a), on)
+    assert same(evaluate(a), on)  # every log_density_gradient builds its own plan
+    a.close()
+    b = make()  # created with the variable unset, flipped afterwards
+    monkeypatch.setenv(var, "1")
+    off_flipped = evaluate(b)
+    b.close()
+    monkeypatch.delenv(var)
+    c = make()  # never sees the variable
+    off = evaluate(c)
+    c.close()
+    assert same(off_flipped, off)
+    assert not np.array_equal(on[0], off[0])  # the two modes differ in bits, so the above can tell them apart
+
+
+def test_gx_exact_fixed_at_context_creation(Ctx, monkeypatch):
+    """BANN_GX_EXACT picks the head's fuse mode, every GEMM's kernel and the tile shapes
+    the plans' prefix arrays count: one value per context, whatever the environment does later"""
+    cfg = dict(n=1500, m=300, widths=[150, 150, 1], act="tanh", prior="ridge_ard")
+    rng, g, snps, br = make_problem(cfg, 53)
+    y = rng.normal(size=cfg["n"]).astype(np.float32).astype(np.float64)
+    _check_switch_fixed_per_context(monkeypatch, "BANN_GX_EXACT",
+                                    lambda: build_context(Ctx, g, [dict(snps=snps, branch=br, y=y)]), "layered")
+
+
 def test_layered_scratch_groups_and_packing(Ctx):
     """gx branches of mixed shapes in several scratch groups (a 1 MiB budget puts
     every branch in its own group, so later groups overwrite the scratch of
@@ -814,6 +857,13 @@ def test_wide_exact_f32_path(Ctx):
             assert norm_rel(grad, ref) < TOL, b
             assert scalar_close(rss, orss)
         assert norm_rel(g_planes[b][0], g_exact[b][0]) < 2e-6
+
+
+def test_wx_exact_fixed_at_context_creation(Ctx, monkeypatch):
+    """BANN_WX_EXACT sizes the wx work split at bann_finalize and picks the kernel of every
+    launch: one value per context, whatever the environment does later"""
+    _check_switch_fixed_per_context(monkeypatch, "BANN_WX_EXACT",
+                                    lambda: _wide_problem(Ctx, 45, nb=2, widths=(32, 27, 1))[0], "wide")
 
 
 def test_wide_bf16_hidden_gemm(Ctx):

@@ -301,6 +301,37 @@ def test_network_hmc_fx_only_matches_oracle(monkeypatch, net_err, big):
     ctx.close()
 
 
+def test_net_err_fixed_at_context_creation(monkeypatch):
+    """BANN_NET_ERR is read once per context, at its creation: of two contexts created under
+    BANN_NET_ERR=0, the one that sees the variable flipped to 1 before its trajectory runs the
+    same trajectory, bit for bit"""
+    monkeypatch.setenv("BANN_NET_ERR", "0")
+    rng = np.random.default_rng(31)
+    n, L = 1500, 4
+    shapes = [(60, [4, 4, 1]), (100, [4, 4, 1]), (33, [4, 3, 1]), (64, [4, 4, 1])]
+    g = O.synthetic_genotypes(rng, n, sum(m for m, _ in shapes))
+    specs, off = [], 0
+    for m, w in shapes:
+        specs.append(dict(snps=np.arange(off, off + m, dtype=np.int32),
+                          branch=f32_branch(O.random_branch(rng, m, w, prior="ridge_ard"))))
+        off += m
+    y = rng.normal(size=n).astype(np.float32)
+    eps, mom = _draws(rng, specs, L)
+    ctxs = [_context(g, specs, range(len(specs))) for _ in range(2)]
+    res = []
+    for ctx, flip in zip(ctxs, (False, True)):
+        assert all(ctx.kernel_path(b) == "fused" for b in range(len(specs)))
+        if flip:
+            monkeypatch.setenv("BANN_NET_ERR", "1")
+        r = ctx.network_hmc_step(y, L, bias=0.1, lambda_e=2.0, eps=np.concatenate(eps),
+                                 momentum=np.concatenate(mom), u=0.5)
+        res.append((r["status"], r["trace"], [ctx.get_params(b) for b in range(len(specs))]))
+        ctx.close()
+    assert res[0][0] == res[1][0]
+    assert np.array_equal(res[0][1], res[1][1])
+    assert all(np.array_equal(a, b) for a, b in zip(res[0][2], res[1][2]))
+
+
 @pytest.mark.parametrize("fx_only", [True, False])
 def test_common_mode_step_rule(fx_only):
     """bann_set_network_step_rule (default on): before the trajectory one gradient launch
