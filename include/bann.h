@@ -444,7 +444,7 @@ int bann_set_network_adapt_trajectories(bann_ctx* ctx, int32_t k);
 int bann_network_step_rule_state(const bann_ctx* ctx, int32_t* mode, int32_t* adapted, int32_t* frozen);
 /* the network sampler's forward: the group-sum rows of its plan (k_forward_gsum: every
  * branch an fx branch of 8 chunks -- each step's forward but the last writes one row per
- * group of four branches), 0 = per-branch output rows, -1 = no network trajectory yet */
+ * item of up to 8R branches), 0 = per-branch output rows, -1 = no network trajectory yet */
 int bann_network_info(const bann_ctx* ctx, int32_t* group_rows);
 /* the last network trajectory's rule: [threshold t (inf: no step changed),
  * (omega eps)^2 of the common mode before (inf when some single parameter alone

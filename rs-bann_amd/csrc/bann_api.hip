@@ -191,65 +191,78 @@ static void step_bases(const BranchHost& h, std::vector<double>& out) {
   }
 }
 
-int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool persistent) {
-  free_plan(p);
+// ---------------------------------------------------------------------------
+// plans: build_plan = validation, three parts (fused groups, gx groups, branch lists), one upload
+// ---------------------------------------------------------------------------
+// the kernel instantiation that serves a fused branch, as the key of its launch group
+static LaunchGroup group_key(const bann_ctx* ctx, const BranchHost& h) {
+  const BranchDev& d = h.dev;
+  LaunchGroup key;
+  key.kind = d.fused;
+  key.act = h.act;
+  if (d.fused == PATH_FX) {  // fx: (L, act, exactly 8 chunks)
+    key.L = h.L;
+    key.full = d.nchunks == 8;
+  } else if (d.fused == PATH_FXL) {  // fxl: (L, act, chunks per wave, waves, every wave full)
+    key.L = h.L;
+    key.cpw = fxl_cpw(d.nchunks, ctx->opt.fxl_cpw);
+    key.nw = (d.nchunks + key.cpw - 1) / key.cpw;
+    key.head = ctx->opt.fxl_head ? 1 : 0;
+    key.full = d.nchunks == key.cpw * key.nw;
+  } else if (d.fused == PATH_WX) {  // wx: (act, marker chunks: the plane kernel is compiled per chunk count)
+    key.nw = d.nchunks;
+  }
+  return key;
+}
+
+// solo mode: too few work items to fill the GPU -> every fused branch re-split
+// into its solo_items items, partials into the solo region, folded afterwards
+static bool plan_goes_solo(const bann_ctx* ctx, const Plan& p) {
+  int64_t items = 0, need = 0, need_rss = 0;
+  for (int32_t b : p.all) {
+    const BranchHost& h = ctx->br[b];
+    if (h.dev.fused == PATH_GX) continue;
+    items += h.dev.nsplits;
+    need += (int64_t)h.solo_items * h.P;
+    need_rss += h.solo_items;
+  }
+  return items > 0 && items < ctx->solo_threshold && need <= ctx->solo_part_cap && need_rss <= ctx->solo_rss_cap;
+}
+
+// the fused update (kernels_fx.hip tail): fx branches only, the small update, one round of items
+static bool plan_fuses_update(const bann_ctx* ctx, const Plan& p, bool solo) {
+  int64_t items = 0;
+  bool ok = p.gx.empty() && ctx->d_upd_cnt != nullptr && ctx->opt.fuse_update;
+  bool single = true;  // every branch one split: its one workgroup updates it
+  for (const auto& g : p.groups) {
+    ok = ok && g.kind == PATH_FX;
+    items += (int64_t)g.items.size();
+  }
+  for (size_t i = 0; i < p.all.size() && ok; ++i) {
+    const BranchHost& h = ctx->br[p.all[i]];
+    ok = h.P <= 2048 && h.m <= 512 && !update_is_large(h.dev);
+    single = single && h.dev.nsplits == 1;
+  }
+  // solo plans: the last arriving workgroup folds the branch's slabs, then updates it
+  return ok && items > 0 && (solo || single || items <= 2ll * ctx->cus);
+}
+
+// part 1: the fused branches of p.all into launch groups of work items (with the solo and
+// fuse-update decisions), the others into p.gx
+static void plan_fused_groups(const bann_ctx* ctx, Plan& p) {
   const int32_t nbr = (int32_t)ctx->br.size();
-  if (nb > nbr) return fail(ctx, BANN_E_ARG, "branch list longer than the branch set");
-  std::vector<char> seen(nbr, 0);
-  for (int i = 0; i < nb; ++i) {
-    const int b = branches[i];
-    if (b < 0 || b >= nbr) return fail(ctx, BANN_E_SHAPE, "branch index out of range");
-    if (seen[b]) return fail(ctx, BANN_E_ARG, "duplicate branch in list");
-    seen[b] = 1;
-  }
-  p.all.assign(branches, branches + nb);
-  std::vector<int32_t> lists(p.all);
-  for (int i = 0; i < nb; ++i)
-    if (!update_is_large(ctx->br[branches[i]].dev)) lists.push_back(branches[i]);
-  p.n_small = (int32_t)lists.size() - nb;
-  for (int i = 0; i < nb; ++i)
-    if (update_is_large(ctx->br[branches[i]].dev)) lists.push_back(branches[i]);
-  p.n_large = nb - p.n_small;
   const int64_t nfrag = ctx->nfrag, ntile = (nfrag + BANN_TILE_FRAGS - 1) / BANN_TILE_FRAGS;
-  // solo mode: too few work items to fill the GPU -> every fused branch re-split
-  // into its solo_items items, partials into the solo region, folded afterwards
-  bool solo = false;
-  {
-    int64_t items = 0, need = 0, need_rss = 0;
-    for (int i = 0; i < nb; ++i) {
-      const BranchHost& h = ctx->br[branches[i]];
-      if (!h.dev.fused) continue;
-      items += h.dev.nsplits;
-      need += (int64_t)h.solo_items * h.P;
-      need_rss += h.solo_items;
-    }
-    solo = items > 0 && items < ctx->solo_threshold && need <= ctx->solo_part_cap && need_rss <= ctx->solo_rss_cap;
-  }
+  const bool solo = plan_goes_solo(ctx, p);
   int64_t solo_part = ctx->part_total, solo_rss = (int64_t)nbr * ctx->max_splits;
-  for (int i = 0; i < nb; ++i) {
-    const int b = branches[i];
+  for (int32_t b : p.all) {
     const BranchHost& h = ctx->br[b];
     const BranchDev& d = h.dev;
     p.max_p = std::max(p.max_p, h.P);
-    if (!d.fused) {
+    if (d.fused == PATH_GX) {
       p.gx.push_back(b);
       continue;
     }
-    LaunchGroup key;
-    key.kind = d.fused;
-    key.act = h.act;
-    if (d.fused == 1) {  // fx: (L, act, exactly 8 chunks)
-      key.L = h.L;
-      key.full = d.nchunks == 8;
-    } else if (d.fused == 3) {  // fxl: (L, act, chunks per wave, waves, every wave full)
-      key.L = h.L;
-      key.cpw = fxl_cpw(d.nchunks, ctx->opt.fxl_cpw);
-      key.nw = (d.nchunks + key.cpw - 1) / key.cpw;
-      key.head = ctx->opt.fxl_head ? 1 : 0;
-      key.full = d.nchunks == key.cpw * key.nw;
-    } else if (d.fused == 2) {  // wx: (act, marker chunks: the plane kernel is compiled per chunk count)
-      key.nw = d.nchunks;
-    }
+    const LaunchGroup key = group_key(ctx, h);
     LaunchGroup* grp = nullptr;
     for (auto& g : p.groups)
       if (g.kind == key.kind && g.L == key.L && g.act == key.act && g.nw == key.nw && g.full == key.full &&
@@ -262,7 +275,7 @@ int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool
     const int spi = 1;  // partial slabs per work item
     const int ns = solo ? h.solo_items : d.nsplits;
     if (grp->items.empty()) grp->fi = true;
-    if (d.fused == 1) {
+    if (d.fused == PATH_FX) {
       grp->fi = grp->fi && d.xi_off >= 0;
       grp->max_seg = std::max(grp->max_seg, (d.nchunks + 3) / 4);
     }
@@ -285,23 +298,11 @@ int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool
       solo_rss += (int64_t)ns * spi;
     }
   }
-  {  // the fused update (kernels_fx.hip tail): fx branches only, the small update, one round of items
-    int64_t items = 0;
-    bool ok = p.gx.empty() && ctx->d_upd_cnt != nullptr && ctx->opt.fuse_update;
-    bool single = true;  // every branch one split: its one workgroup updates it
-    for (const auto& g : p.groups) {
-      ok = ok && g.kind == 1;
-      items += (int64_t)g.items.size();
-    }
-    for (int i = 0; i < nb && ok; ++i) {
-      const BranchHost& h = ctx->br[branches[i]];
-      ok = h.P <= 2048 && h.m <= 512 && !update_is_large(h.dev);
-      single = single && h.dev.nsplits == 1;
-    }
-    // solo plans: the last arriving workgroup folds the branch's slabs, then updates it
-    p.fuse_update = ok && items > 0 && (solo || single || items <= 2ll * ctx->cus);
-  }
-  // gx branches: grouped by scratch group, one tile prefix array per GEMM phase
+  p.fuse_update = plan_fuses_update(ctx, p, solo);
+}
+
+// part 2: the gx branches grouped by scratch group, one tile prefix array per GEMM phase
+static int plan_gx_groups(bann_ctx* ctx, Plan& p) {
   std::stable_sort(p.gx.begin(), p.gx.end(),
                    [&](int32_t a, int32_t b) { return ctx->br[a].gx_group < ctx->br[b].gx_group; });
   for (size_t i = 0; i < p.gx.size();) {
@@ -343,65 +344,135 @@ int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool
     p.gxg.push_back(std::move(g));
     i = j;
   }
-  if (persistent) {
-    p.owns = true;
-    CK(dalloc(&p.d_all, 2 * nb));
-    CK(dalloc(&p.d_gx, (int64_t)p.gx.size()));
-    CK(dalloc(&p.d_gxpre, (int64_t)p.gx_pre.size()));
-    CK(dalloc(&p.d_fold, (int64_t)p.fold.size()));
-    if (!p.fold.empty())
-      CK(hipMemcpyAsync(p.d_fold, p.fold.data(), p.fold.size() * sizeof(FoldJob), hipMemcpyHostToDevice,
-                        ctx->stream));
-    CK(hipMemcpyAsync(p.d_all, lists.data(), 2 * nb * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (!p.gx.empty()) {
-      CK(hipMemcpyAsync(p.d_gx, p.gx.data(), p.gx.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-      CK(hipMemcpyAsync(p.d_gxpre, p.gx_pre.data(), p.gx_pre.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                        ctx->stream));
-    }
-    for (auto& g : p.groups) {
-      CK(dalloc(&g.d_items, (int64_t)g.items.size()));
-      CK(hipMemcpyAsync(g.d_items, g.items.data(), g.items.size() * sizeof(GradItem), hipMemcpyHostToDevice,
-                        ctx->stream));
-    }
-  } else {
-    p.owns = false;
-    p.d_all = ctx->d_list_scr;
-    p.d_gx = ctx->d_gen_scr;
-    p.d_gxpre = ctx->d_gxpre_scr;
-    p.d_fold = ctx->d_fold_scr;
-    if ((int64_t)p.gx_pre.size() > ctx->gxpre_cap) return fail(ctx, BANN_E_STATE, "gx plan scratch overflow");
-    if (ctx->plan_ev_pending) CK(hipEventSynchronize(ctx->ev_plan));  // the last plan's copy has read the stage
-    char* hs = ctx->h_plan_stage;
-    std::memcpy(hs, lists.data(), 2 * nb * sizeof(int32_t));
-    int64_t end = 2 * (int64_t)nb * (int64_t)sizeof(int32_t);
-    if (!p.fold.empty()) {
-      std::memcpy(hs + ctx->plan_off_fold, p.fold.data(), p.fold.size() * sizeof(FoldJob));
-      end = ctx->plan_off_fold + (int64_t)(p.fold.size() * sizeof(FoldJob));
-    }
-    if (!p.gx.empty()) {
-      CK(hipMemcpyAsync(p.d_gx, p.gx.data(), p.gx.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-      CK(hipMemcpyAsync(p.d_gxpre, p.gx_pre.data(), p.gx_pre.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                        ctx->stream));
-    }
-    int64_t off = 0;
-    for (auto& g : p.groups) {
-      if (off + (int64_t)g.items.size() > ctx->items_cap) return fail(ctx, BANN_E_STATE, "work-item scratch overflow");
-      g.d_items = ctx->d_items_scr + off;
-      std::memcpy(hs + ctx->plan_off_items + off * (int64_t)sizeof(GradItem), g.items.data(),
-                  g.items.size() * sizeof(GradItem));
-      off += (int64_t)g.items.size();
-    }
-    if (off > 0) end = ctx->plan_off_items + off * (int64_t)sizeof(GradItem);
-    CK(hipMemcpyAsync(ctx->d_plan_scr, hs, (size_t)end, hipMemcpyHostToDevice, ctx->stream));
-    CK(hipEventRecord(ctx->ev_plan, ctx->stream));
-    ctx->plan_ev_pending = true;
+  return BANN_OK;
+}
+
+// part 3: the device branch lists: p.all, then the update kernels' small and large branches
+static std::vector<int32_t> plan_branch_lists(const bann_ctx* ctx, Plan& p) {
+  const int32_t nb = (int32_t)p.all.size();
+  std::vector<int32_t> lists(p.all);
+  for (int32_t b : p.all)
+    if (!update_is_large(ctx->br[b].dev)) lists.push_back(b);
+  p.n_small = (int32_t)lists.size() - nb;
+  for (int32_t b : p.all)
+    if (update_is_large(ctx->br[b].dev)) lists.push_back(b);
+  p.n_large = nb - p.n_small;
+  return lists;
+}
+
+// a persistent plan owns its device arrays
+static int upload_plan_persistent(bann_ctx* ctx, Plan& p, const std::vector<int32_t>& lists) {
+  const int32_t nb = (int32_t)p.all.size();
+  p.owns = true;
+  CK(dalloc(&p.d_all, 2 * nb));
+  CK(dalloc(&p.d_gx, (int64_t)p.gx.size()));
+  CK(dalloc(&p.d_gxpre, (int64_t)p.gx_pre.size()));
+  CK(dalloc(&p.d_fold, (int64_t)p.fold.size()));
+  if (!p.fold.empty())
+    CK(hipMemcpyAsync(p.d_fold, p.fold.data(), p.fold.size() * sizeof(FoldJob), hipMemcpyHostToDevice, ctx->stream));
+  CK(hipMemcpyAsync(p.d_all, lists.data(), 2 * nb * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  if (!p.gx.empty()) {
+    CK(hipMemcpyAsync(p.d_gx, p.gx.data(), p.gx.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    CK(hipMemcpyAsync(p.d_gxpre, p.gx_pre.data(), p.gx_pre.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                      ctx->stream));
+  }
+  for (auto& g : p.groups) {
+    CK(dalloc(&g.d_items, (int64_t)g.items.size()));
+    CK(hipMemcpyAsync(g.d_items, g.items.data(), g.items.size() * sizeof(GradItem), hipMemcpyHostToDevice,
+                      ctx->stream));
   }
   return BANN_OK;
 }
 
+// a per-call plan lives in the context's plan scratch: lists, fold jobs and work items through
+// the pinned stage in one copy (offsets: plan_layout)
+static int upload_plan_scratch(bann_ctx* ctx, Plan& p, const std::vector<int32_t>& lists) {
+  const int32_t nb = (int32_t)p.all.size();
+  p.owns = false;
+  p.d_all = ctx->d_list_scr;
+  p.d_gx = ctx->d_gen_scr;
+  p.d_gxpre = ctx->d_gxpre_scr;
+  p.d_fold = ctx->d_fold_scr;
+  if ((int64_t)p.gx_pre.size() > ctx->gxpre_cap) return fail(ctx, BANN_E_STATE, "gx plan scratch overflow");
+  if (ctx->plan_ev_pending) CK(hipEventSynchronize(ctx->ev_plan));  // the last plan's copy has read the stage
+  char* hs = ctx->h_plan_stage;
+  std::memcpy(hs, lists.data(), 2 * nb * sizeof(int32_t));
+  int64_t end = 2 * (int64_t)nb * (int64_t)sizeof(int32_t);
+  if (!p.fold.empty()) {
+    std::memcpy(hs + ctx->plan_off_fold, p.fold.data(), p.fold.size() * sizeof(FoldJob));
+    end = ctx->plan_off_fold + (int64_t)(p.fold.size() * sizeof(FoldJob));
+  }
+  if (!p.gx.empty()) {
+    CK(hipMemcpyAsync(p.d_gx, p.gx.data(), p.gx.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    CK(hipMemcpyAsync(p.d_gxpre, p.gx_pre.data(), p.gx_pre.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                      ctx->stream));
+  }
+  int64_t off = 0;
+  for (auto& g : p.groups) {
+    if (off + (int64_t)g.items.size() > ctx->items_cap) return fail(ctx, BANN_E_STATE, "work-item scratch overflow");
+    g.d_items = ctx->d_items_scr + off;
+    std::memcpy(hs + ctx->plan_off_items + off * (int64_t)sizeof(GradItem), g.items.data(),
+                g.items.size() * sizeof(GradItem));
+    off += (int64_t)g.items.size();
+  }
+  if (off > 0) end = ctx->plan_off_items + off * (int64_t)sizeof(GradItem);
+  CK(hipMemcpyAsync(ctx->d_plan_scr, hs, (size_t)end, hipMemcpyHostToDevice, ctx->stream));
+  CK(hipEventRecord(ctx->ev_plan, ctx->stream));
+  ctx->plan_ev_pending = true;
+  return BANN_OK;
+}
+
+int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool persistent) {
+  free_plan(p);
+  const int32_t nbr = (int32_t)ctx->br.size();
+  if (nb > nbr) return fail(ctx, BANN_E_ARG, "branch list longer than the branch set");
+  std::vector<char> seen(nbr, 0);
+  for (int i = 0; i < nb; ++i) {
+    const int b = branches[i];
+    if (b < 0 || b >= nbr) return fail(ctx, BANN_E_SHAPE, "branch index out of range");
+    if (seen[b]) return fail(ctx, BANN_E_ARG, "duplicate branch in list");
+    seen[b] = 1;
+  }
+  p.all.assign(branches, branches + nb);
+  plan_fused_groups(ctx, p);
+  const int rc = plan_gx_groups(ctx, p);
+  if (rc) return rc;
+  const std::vector<int32_t> lists = plan_branch_lists(ctx, p);
+  return persistent ? upload_plan_persistent(ctx, p, lists) : upload_plan_scratch(ctx, p, lists);
+}
+
 // launch_fused_grad_wx's mode: bf16 MFMA when opted in, else the exact-f32 MFMA (BANN_WX_EXACT=1) or the
-// f32-accurate bf16 planes; bann_finalize sized the wx splits for the same choice
+// f32-accurate bf16 planes; plan_layout sized the wx splits for the same choice
 static int wx_mode(const bann_ctx* ctx) { return ctx->wide_bf16 ? 1 : (ctx->opt.wx_exact ? 0 : 2); }
+
+// the gradient launch of one fused group; upd_mode, upd_step, cnt, fo: fx's fused update (run_grad)
+static void launch_group_grad(const bann_ctx* ctx, const DevState& s, const LaunchGroup& g, int wp, int upd_mode,
+                              int upd_step, int32_t* cnt, const FoldJob* fo) {
+  const int32_t ni = (int32_t)g.items.size();
+  if (g.kind == PATH_WX)
+    launch_fused_grad_wx(s, g.d_items, ni, g.act, wx_mode(ctx), g.nw, wp, ctx->stream);
+  else if (g.kind == PATH_FXL)
+    launch_fused_grad_fxl(s, g.d_items, ni, g.L, g.act, g.nw, g.cpw, g.full, wp, g.head, ctx->stream);
+  else
+    launch_fused_grad_fx(s, g.d_items, ni, g.L, g.act, g.full, wp, upd_mode, upd_step, cnt, fo, ctx->stream);
+}
+
+// gx branches: scratch group by scratch group (the groups reuse one scratch), every phase of
+// the group, or up to the head only: it writes the predictions, the backward is not needed
+static void launch_gx_phases(const bann_ctx* ctx, const DevState& s, const Plan& p, bool head_only) {
+  for (const auto& g : p.gxg) {
+    const int32_t* bl = p.d_gx + g.first;
+    launch_gx_prep(s, bl, g.count, ctx->stream);
+    for (const auto& ph : g.phases) {
+      if (ph.ph == GX_HEAD) {
+        launch_gx_head(s, bl, g.count, g.max_splits, ctx->opt.gx_exact, ctx->stream);
+        if (head_only) break;
+      } else {
+        launch_gx_gemm(s, ph.ph, ph.l, bl, p.d_gxpre + ph.pre_off, g.count, ph.total, ctx->opt.gx_exact, ctx->stream);
+      }
+    }
+  }
+}
 
 // gradient (partials) of every branch in the plan at the current theta.
 // write_pred: 0 = no predictions (the layered path writes them anyway), 1 = the
@@ -416,27 +487,9 @@ int run_grad(bann_ctx* ctx, const Plan& p, int write_pred, int upd_mode, int upd
   int32_t* cnt = upd_mode >= 0 ? ctx->d_upd_cnt : nullptr;
   // a fused solo plan folds in the gradient launch's tail (kernels_fx.hip), not in k_fold_solo
   const FoldJob* fo = (cnt && !p.fold.empty()) ? p.d_fold : nullptr;
-  for (const auto& g : p.groups) {
-    const int32_t ni = (int32_t)g.items.size();
-    if (g.kind == 2)
-      launch_fused_grad_wx(s, g.d_items, ni, g.act, wx_mode(ctx), g.nw, wp, ctx->stream);
-    else if (g.kind == 3)
-      launch_fused_grad_fxl(s, g.d_items, ni, g.L, g.act, g.nw, g.cpw, g.full, wp, g.head, ctx->stream);
-    else
-      launch_fused_grad_fx(s, g.d_items, ni, g.L, g.act, g.full, wp, upd_mode, upd_step, cnt, fo, ctx->stream);
-  }
+  for (const auto& g : p.groups) launch_group_grad(ctx, s, g, wp, upd_mode, upd_step, cnt, fo);
   if (!p.fold.empty() && !fo) launch_fold_solo(s, p.d_fold, (int32_t)p.fold.size(), p.max_p, ctx->stream);
-  // gx branches: scratch group by scratch group (the groups reuse one scratch)
-  for (const auto& g : p.gxg) {
-    const int32_t* bl = p.d_gx + g.first;
-    launch_gx_prep(s, bl, g.count, ctx->stream);
-    for (const auto& ph : g.phases) {
-      if (ph.ph == GX_HEAD)
-        launch_gx_head(s, bl, g.count, g.max_splits, ctx->opt.gx_exact, ctx->stream);
-      else
-        launch_gx_gemm(s, ph.ph, ph.l, bl, p.d_gxpre + ph.pre_off, g.count, ph.total, ctx->opt.gx_exact, ctx->stream);
-    }
-  }
+  launch_gx_phases(ctx, s, p, false);
   CK(hipGetLastError());
   if (write_pred == 1) mark_predictions(ctx, p, true);
   return BANN_OK;
@@ -449,27 +502,15 @@ int run_forward(bann_ctx* ctx, const Plan& p) {
   const DevState& s = ctx->st;
   for (const auto& g : p.groups) {
     const int32_t ni = (int32_t)g.items.size();
-    if (g.kind == 2)
-      launch_fused_grad_wx(s, g.d_items, ni, g.act, wx_mode(ctx), g.nw, 1, ctx->stream);
-    else if (g.kind == 3)
-      launch_fused_grad_fxl(s, g.d_items, ni, g.L, g.act, g.nw, g.cpw, g.full, 1, g.head, ctx->stream);
+    if (g.kind != PATH_FX)
+      launch_group_grad(ctx, s, g, 1, -1, 0, nullptr, nullptr);
     else if (g.fi)
       launch_forward_fi(s, g.d_items, ni, g.tiles, g.L, g.act, g.max_seg, ctx->cus, ctx->opt.fi_waves_per_simd,
                         ctx->stream);
     else
       launch_forward_fx(s, g.d_items, ni, g.L, g.act, g.full, ctx->stream);
   }
-  for (const auto& g : p.gxg) {
-    const int32_t* bl = p.d_gx + g.first;
-    launch_gx_prep(s, bl, g.count, ctx->stream);
-    for (const auto& ph : g.phases) {
-      if (ph.ph == GX_HEAD) {
-        launch_gx_head(s, bl, g.count, g.max_splits, ctx->opt.gx_exact, ctx->stream);
-        break;  // the head writes the predictions; the backward phases are not needed
-      }
-      launch_gx_gemm(s, ph.ph, ph.l, bl, p.d_gxpre + ph.pre_off, g.count, ph.total, ctx->opt.gx_exact, ctx->stream);
-    }
-  }
+  launch_gx_phases(ctx, s, p, true);
   CK(hipGetLastError());
   mark_predictions(ctx, p, true);
   return BANN_OK;
@@ -704,41 +745,12 @@ extern "C" int bann_branch_add(bann_ctx* ctx, const int32_t* snp_idx, int32_t m,
   if (layer_widths[num_layers - 1] != 1) return fail(ctx, BANN_E_SHAPE, "output layer width must be 1");
   if (activation < 0 || activation > 4) return fail(ctx, BANN_E_ARG, "unknown activation");
   if (prior < 0 || prior > 4) return fail(ctx, BANN_E_ARG, "unknown prior");
-  BranchHost h;
-  h.snp_idx.assign(snp_idx, snp_idx + m);
-  h.widths.assign(layer_widths, layer_widths + num_layers);
   for (int l = 0; l < num_layers; ++l)
-    if (h.widths[l] <= 0) return fail(ctx, BANN_E_SHAPE, "layer widths must be positive");
+    if (layer_widths[l] <= 0) return fail(ctx, BANN_E_SHAPE, "layer widths must be positive");
   for (int i = 0; i < m; ++i)
     if (snp_idx[i] < 0 || (ctx->M > 0 && snp_idx[i] >= ctx->M))
       return fail(ctx, BANN_E_SHAPE, "marker index out of range");
-  h.m = m;
-  h.L = num_layers;
-  h.act = activation;
-  h.prior = prior;
-  BranchDev& d = h.dev;
-  d.m = m;
-  d.L = num_layers;
-  d.act = activation;
-  d.prior = prior;
-  int off = 0;
-  for (int l = 0; l < num_layers; ++l) {
-    d.widths[l] = h.widths[l];
-    d.win[l] = l == 0 ? m : h.widths[l - 1];
-    d.woff[l] = off;
-    off += d.win[l] * d.widths[l];
-  }
-  for (int l = 0; l < num_layers - 1; ++l) {
-    d.boff[l] = off;
-    off += d.widths[l];
-  }
-  d.P = h.P = off;
-  const bool ard = (prior == BANN_RIDGE_ARD || prior == BANN_LASSO_ARD);
-  int np = 0;
-  for (int l = 0; l < num_layers; ++l) np += (ard && l < num_layers - 1) ? d.win[l] : 1;
-  h.nprec = np + (num_layers - 1) + 1;
-  h.prec.assign(h.nprec, 1.f);
-  ctx->br.push_back(std::move(h));
+  ctx->br.push_back(make_branch(snp_idx, m, layer_widths, num_layers, activation, prior));
   return (int)ctx->br.size() - 1;
 }
 
@@ -789,241 +801,59 @@ extern "C" int bann_set_graph_replay(bann_ctx* ctx, int32_t enabled) {
 extern "C" int bann_get_graph_replay(const bann_ctx* ctx) { return ctx ? (ctx->graph_replay ? 1 : 0) : BANN_E_ARG; }
 extern "C" int64_t bann_packed_genotype_bytes(const bann_ctx* ctx) { return ctx ? ctx->packed_bytes : 0; }
 
-extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
-  if (!ctx) return BANN_E_ARG;
-  if (ctx->finalized) return fail(ctx, BANN_E_STATE, "already finalized");
-  if (!ctx->d_g) return fail(ctx, BANN_E_STATE, "no genotypes uploaded");
-  if (ctx->br.empty()) return fail(ctx, BANN_E_STATE, "no branches");
-  CK(hipSetDevice(ctx->device));
-  const int64_t n = ctx->n;
-  ctx->nfrag = (int32_t)((n + 15) / 16);
-  // kernel path per branch: fx (widths <= 4, <= 8 chunks), fxl (widths <= 4,
-  // 9..64 chunks), wx (one hidden layer up to 32 x 32, m <= 128), else gx (layered MFMA GEMMs)
-  int64_t total_frags = 0;
-  for (auto& h : ctx->br) {
-    for (int i = 0; i < h.m; ++i)
-      if (h.snp_idx[i] >= ctx->M) return fail(ctx, BANN_E_SHAPE, "marker index out of range");
-    BranchDev& d = h.dev;
-    d.nchunks = (h.m + BANN_CHUNK - 1) / BANN_CHUNK;
-    bool narrow = ctx->fused_enabled && h.L >= 2 && h.L <= 4;
-    for (int l = 0; l < h.L; ++l) narrow = narrow && h.widths[l] <= BANN_FUSED_MAXW;
-    d.fused = 0;
-    if (narrow && d.nchunks <= BANN_FX_MAXCH)
-      d.fused = 1;
-    else if (narrow && d.nchunks <= BANN_FXL_MAXCH)
-      d.fused = 3;
-    else if (ctx->fused_enabled && h.L == 3 && d.nchunks <= BANN_WIDE_MAXCH && h.widths[0] <= BANN_WIDE_MAXW &&
-             h.widths[1] <= BANN_WIDE_MAXW)
-      d.fused = 2;
-    if (d.fused) total_frags += ctx->nfrag;
-  }
-  const EnvOptions& opt = ctx->opt;
-  // wx (and fx with BANN_TARGET_ITEMS / BANN_MIN_FRAGS): ~target_items work items (default 1024) of at
-  // least min_frags fragments (default 64: >= 16 tiles per work item amortises the per-item prologue/epilogue)
-  const int64_t frags_per_item =
-      std::max<int64_t>(opt.min_frags, (total_frags + opt.target_items - 1) / opt.target_items);
-  const int64_t ntile = (ctx->nfrag + BANN_TILE_FRAGS - 1) / BANN_TILE_FRAGS;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0)
-    cus = 256;
-  ctx->cus = cus;
-  // Splits: whole rounds of resident workgroups.  All items of a packed launch
-  // are equally long, so a launch costs ceil(items / slots) rounds of (per-item
-  // prologue/epilogue + tiles per wave); choose the split count minimising that
-  // (e.g. 125 fx branches on one GPU of an 8-GPU shard: 4 splits = 500 items in
-  // one round, where a 1024-item target gave 9 splits = 1125 items in 3 partly
-  // empty rounds).  Lower bound: <= BANN_MAX_TILES_PER_WAVE tiles per wave, so
-  // the int32 dW0 digit sums cannot overflow.
-  auto best_splits = [&](int64_t nbr, int64_t slots, int64_t tiles_per_split_wave_div) -> int32_t {
-    const int64_t min_sp = (ntile + tiles_per_split_wave_div * BANN_MAX_TILES_PER_WAVE - 1) /
-                           (tiles_per_split_wave_div * BANN_MAX_TILES_PER_WAVE);
-    int32_t best_sp = (int32_t)std::max<int64_t>(1, min_sp);
-    double best = -1.0;
-    for (int64_t sp = std::max<int64_t>(1, min_sp); nbr > 0 && sp <= std::max<int64_t>(64, min_sp); ++sp) {
-      if (sp > min_sp && tiles_per_split_wave_div * sp > ntile) break;
-      const int64_t rounds = (nbr * sp + slots - 1) / slots;
-      const int64_t per_wave = (ntile + tiles_per_split_wave_div * sp - 1) / (tiles_per_split_wave_div * sp);
-      const double cost = (double)rounds * (2.0 + (double)per_wave);  // ~2 tiles of prologue + epilogue
-      if (best < 0.0 || cost < best) best = cost, best_sp = (int32_t)sp;
-    }
-    return best_sp;
-  };
-  int64_t nfx = 0, nfxl[2][9] = {};  // fxl branches by (chunks per wave 4?, waves)
-  auto fxl_key = [&](int nch, int& c4, int& nw) {
-    const int cpw = fxl_cpw(nch, opt.fxl_cpw);
-    c4 = cpw == 4;
-    nw = (nch + cpw - 1) / cpw;
-  };
-  for (auto& h : ctx->br) {
-    if (h.dev.fused == 1) ++nfx;
-    if (h.dev.fused == 3) {
-      int c4, nw;
-      fxl_key(h.dev.nchunks, c4, nw);
-      ++nfxl[c4][nw];
-    }
-  }
-  const int32_t fx_splits = best_splits(nfx, 2 * (int64_t)cus, 4);  // fx: 2 workgroups of 4 waves per CU, tiles interleaved
-  int64_t nwx = 0;
-  for (auto& h : ctx->br) nwx += h.dev.fused == 2;
-  // wx: 4 two-wave workgroups per CU, a tile at a time (exact f32 MFMA); wx3: 2
-  // four-wave workgroups per CU, two tiles at a time
-  const int32_t wx_splits = opt.wx_exact ? best_splits(nwx, 4 * (int64_t)cus, 1) : best_splits(nwx, 2 * (int64_t)cus, 2);
-  int32_t fxl_splits[2][9] = {};
-  for (int c4 = 0; c4 < 2; ++c4)
-    for (int nw = 1; nw <= 8; ++nw) {  // fxl: all waves of a workgroup on one tile; LDS- and VGPR-limited residency
-      const int64_t per_cu =
-          std::max<int64_t>(1, std::min<int64_t>(163840 / fxl_lds_bytes(nw, 4, c4 ? 4 : 8), 8 / nw));
-      fxl_splits[c4][nw] = best_splits(nfxl[c4][nw], per_cu * cus, 1);
-    }
-  int64_t q_off = 0;
-  // forward-only fi images (kernels_fi.hip) for the fx branches with BANN_FWD_FI=1; by default
-  // the LDS forward (k_forward_fx): inside the network trajectory, interleaved with the
-  // gradient launches, it measured faster (2.573 vs 2.660 ms per step, r4c/r4d), and it
-  // needs no second 2-bit image
-  const bool fi_on = opt.fwd_fi;
-  int64_t xi_off = 0;
-  int64_t x2_off = 0, dig_off = 0, p_off = 0, mk_off = 0, part_off = 0, scr_off = 0, items = 0;
-  // gx scratch groups: branches in index order until the budget (BANN_GX_SCRATCH_MB,
-  // default a quarter of the free device memory, at most 64 GiB) is full; every
-  // group reuses the same device scratch.  Fewer, larger groups fill the GPU better
-  // (c3def: 8 GiB = 40 branches per group 335 ms per evaluation, 32 GiB 321 ms)
-  const int64_t gx_rows = ntile * 64;
-  int64_t gx_budget = 8192ll << 18;  // floats
-  {
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 0)
-      gx_budget = std::max<int64_t>(gx_budget, std::min<int64_t>((int64_t)(fr / 4) / 4, 65536ll << 18));
-  }
-  if (opt.gx_scratch_mb > 0) gx_budget = opt.gx_scratch_mb << 18;
-  int64_t gx_cur = 0, n_gx = 0;
-  int32_t gx_ngroups = 0;
-  int32_t max_splits = 1;
-  for (size_t b = 0; b < ctx->br.size(); ++b) {
-    BranchHost& h = ctx->br[b];
-    BranchDev& d = h.dev;
-    d.x_off = x2_off;  // byte offset of the branch's 2-bit tile image: [tile][chunk][1 KiB]
-    x2_off += ntile * d.nchunks * 1024;
-    d.xi_off = -1;  // fx branches: the individual-major image of the forward-only pass, [frag][segment][1 KiB]
-    if (d.fused == 1 && fi_on) {
-      d.xi_off = xi_off;
-      xi_off += 4 * ntile * ((d.nchunks + 3) / 4) * 1024;
-    }
-    d.dig_off = dig_off;
-    if (d.fused) dig_off += (int64_t)d.nchunks * 1024 * (d.fused == 2 ? 8 : 1);
-    d.p_off = p_off;
-    p_off += h.P;
-    {  // precision coordinates in precision_vec order (params.rs:272-289)
-      const bool ard = (h.prior == BANN_RIDGE_ARD || h.prior == BANN_LASSO_ARD);
-      int qo = 0;
-      for (int l = 0; l < h.L; ++l) {
-        d.qoff[l] = qo;
-        qo += (ard && l < h.L - 1) ? d.win[l] : 1;
-      }
-      d.qbias = qo;
-      d.nq = qo + (h.L - 1) + 1;
-      d.q_off = q_off;
-      q_off += d.nq;
-    }
-    d.mk_off = mk_off;
-    mk_off += h.m;
-    d.y_off = (int64_t)b * n;
-    // gx: row splits of ~64 tiles (4096 individuals) for the K = n gradient GEMMs
-    d.nsplits = d.fused ? (int32_t)std::max<int64_t>(1, (ctx->nfrag + frags_per_item - 1) / frags_per_item)
-                        : (int32_t)((ntile + 63) / 64);
-    if (d.fused == 1 && !opt.env_split) d.nsplits = fx_splits;
-    if (d.fused == 3) {
-      int c4, nw;
-      fxl_key(d.nchunks, c4, nw);
-      d.nsplits = fxl_splits[c4][nw];
-    }
-    if (d.fused == 2) d.nsplits = wx_splits;
-    if (d.fused == 1)  // overflow guard also under the env overrides
-      d.nsplits = std::max<int32_t>(d.nsplits, (int32_t)((ntile + 4 * BANN_MAX_TILES_PER_WAVE - 1) /
-                                                         (4 * BANN_MAX_TILES_PER_WAVE)));
-    d.nsplits = (int32_t)std::max<int64_t>(1, std::min<int64_t>(d.nsplits, ntile));
-    if (d.fused) items += d.nsplits;
-    max_splits = std::max(max_splits, d.nsplits);
-    d.part_off = part_off;
-    part_off += (int64_t)d.nsplits * h.P;
-    if (!d.fused) {  // gx scratch (kernels_gx.hip): padded weights, biases, A_l and H_l per layer
-      if (d.widths[h.L - 2] > GX_HEAD_MAXW) return fail(ctx, BANN_E_SHAPE, "summary layer wider than 4096");
-      auto r4 = [](int64_t v) { return (v + 3) & ~3ll; };
-      int64_t o = 0;
-      for (int l = 0; l < h.L; ++l) {
-        d.gx_wld[l] = (int32_t)r4(d.win[l]);
-        d.gx_w[l] = (int32_t)o;
-        o += (int64_t)d.widths[l] * d.gx_wld[l];
-      }
-      for (int l = 0; l < h.L - 1; ++l) {
-        d.gx_b[l] = (int32_t)o;
-        o += r4(d.widths[l]);
-      }
-      d.gx_w0p = (int32_t)o;  // 3 x w0 x 64 nchunks bf16
-      o += r4((3ll * d.widths[0] * 64 * d.nchunks + 1) / 2);
-      for (int l = 1; l < h.L - 1; ++l) {  // 3 x w_l x r32(win_l) bf16
-        d.gx_wp[l] = (int32_t)o;
-        o += r4((3ll * d.widths[l] * ((d.win[l] + 31) & ~31) + 1) / 2);
-      }
-      d.gx_dwo = (int32_t)o;
-      o += 2 * ntile * r4(d.widths[h.L - 2]);
-      d.gx_rss = (int32_t)o;
-      o += r4(2 * ntile);
-      d.gx_op = (int32_t)o;
-      o += 2 * ((d.widths[h.L - 2] + 63) / 64) * gx_rows;
-      d.gx_e = (int32_t)o;
-      o += gx_rows;
-      d.gx_wps = (int32_t)o;
-      if (h.L >= 3) o += r4((3ll * d.widths[h.L - 2] * ((d.win[h.L - 2] + 31) & ~31) + 1) / 2);
-      for (int l = 0; l < h.L - 1; ++l) {
-        d.gx_ld[l] = (int32_t)r4(d.widths[l]);
-        d.gx_a[l] = (int32_t)o;
-        o += gx_rows * d.gx_ld[l];
-        d.gx_h[l] = (int32_t)o;
-        o += gx_rows * d.gx_ld[l];
-        if (o >= (1ll << 31)) return fail(ctx, BANN_E_SHAPE, "gx scratch of one branch exceeds 2^31 floats");
-      }
-      if (gx_cur > 0 && gx_cur + o > gx_budget) {  // a new scratch group
-        ++gx_ngroups;
-        gx_cur = 0;
-      }
-      h.gx_group = gx_ngroups;
-      d.scr_off = gx_cur;
-      gx_cur += o;
-      scr_off = std::max(scr_off, gx_cur);
-      ++n_gx;
-    }
-  }
-  ctx->max_splits = max_splits;
-  // solo mode (build_plan): ~one tile per wave for a branch alone on the GPU
-  // (BANN_SOLO_TPW: more tiles per wave, fewer slabs to fold)
-  const int64_t solo_tpw = opt.solo_tpw;
-  int64_t max_p_fused = 0;
-  for (auto& h : ctx->br) {
+// ---------------------------------------------------------------------------
+// finalize: plan_layout (finalize_layout.h) decides, the steps below allocate, pack and upload
+// ---------------------------------------------------------------------------
+// floats of one gx scratch group: BANN_GX_SCRATCH_MB, default a quarter of the free device
+// memory, at least 8 and at most 64 GiB
+static int64_t gx_scratch_budget(const EnvOptions& opt) {
+  int64_t budget = 8192ll << 18;
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 0)
+    budget = std::max<int64_t>(budget, std::min<int64_t>((int64_t)(fr / 4) / 4, 65536ll << 18));
+  return opt.gx_scratch_mb > 0 ? opt.gx_scratch_mb << 18 : budget;
+}
+
+// the host arrays that bann_finalize's asynchronous copies read and the temporary device
+// arrays of its pack launches: alive until its steps have synchronised
+struct FinalizeStage {
+  std::vector<int32_t> allidx;  // the branches' marker indices, concatenated
+  std::vector<PackJob> jobs;
+  std::vector<BranchDev> descs;
+  std::vector<float> eprec;
+  int32_t* d_idx = nullptr;
+  PackJob* d_jobs = nullptr;
+  PackJob* d_fijobs = nullptr;
+};
+
+// parameter -> precision index (within the branch), for the joint update
+static std::vector<int32_t> precision_index(const std::vector<BranchHost>& br, int64_t total_p) {
+  std::vector<int32_t> pidx(total_p);
+  for (auto& h : br) {
     const BranchDev& d = h.dev;
-    if (!d.fused) continue;
-    max_p_fused = std::max<int64_t>(max_p_fused, h.P);
-    // fx: 4 waves on their own tiles, solo_tpw tiles each; fxl / wx: a tile at a time
-    const int64_t per_item = d.fused == 1 ? 4 * solo_tpw : 1;
-    h.solo_items = (int32_t)std::max<int64_t>(d.nsplits,
-                                              std::min<int64_t>(2 * cus, (ntile + per_item - 1) / per_item));
+    const bool ard = (h.prior == BANN_RIDGE_ARD || h.prior == BANN_LASSO_ARD);
+    for (int l = 0; l < h.L; ++l)
+      for (int k = 0; k < d.widths[l]; ++k)
+        for (int j = 0; j < d.win[l]; ++j)
+          pidx[d.p_off + d.woff[l] + (int64_t)k * d.win[l] + j] = d.qoff[l] + ((ard && l < h.L - 1) ? j : 0);
+    for (int l = 0; l < h.L - 1; ++l)
+      for (int k = 0; k < d.widths[l]; ++k) pidx[d.p_off + d.boff[l] + k] = d.qbias + l;
   }
-  ctx->solo_threshold = opt.solo ? cus : 0;  // BANN_SOLO=0: never re-split
-  ctx->solo_rss_cap = 8ll * cus;
-  ctx->solo_part_cap = ctx->solo_rss_cap * max_p_fused;
-  ctx->part_total = part_off;
-  ctx->packed_bytes = x2_off;
-  ctx->total_p = p_off;
-  ctx->total_q = q_off;
-  const int64_t nb = (int64_t)ctx->br.size();
-  CK(dalloc(&ctx->d_xu2, x2_off));
-  ctx->xi_bytes = xi_off;
-  if (xi_off > 0) CK(dalloc(&ctx->d_xi, xi_off));
-  CK(dalloc(&ctx->d_dig, dig_off));
-  CK(hipMemsetAsync(ctx->d_dig, 0, (size_t)std::max<int64_t>(dig_off, 1), ctx->stream));
+  return pidx;
+}
+
+// the images, the parameter- and precision-sized arrays, the partial slabs and the n-vectors
+static int alloc_branch_state(bann_ctx* ctx, const LayoutTotals& t) {
+  const int64_t n = ctx->n, nb = (int64_t)ctx->br.size(), p_off = t.total_p;
+  CK(dalloc(&ctx->d_xu2, t.tile_bytes));
+  ctx->xi_bytes = t.fi_bytes;
+  if (t.fi_bytes > 0) CK(dalloc(&ctx->d_xi, t.fi_bytes));
+  CK(dalloc(&ctx->d_dig, t.dig_bytes));
+  CK(hipMemsetAsync(ctx->d_dig, 0, (size_t)std::max<int64_t>(t.dig_bytes, 1), ctx->stream));
   CK(dalloc(&ctx->d_fc, nb));
   CK(hipMemsetAsync(ctx->d_fc, 0, nb * sizeof(FusedConst), ctx->stream));
-  CK(dalloc(&ctx->d_mub, mk_off));
-  CK(dalloc(&ctx->d_sigb, mk_off));
+  CK(dalloc(&ctx->d_mub, t.total_markers));
+  CK(dalloc(&ctx->d_sigb, t.total_markers));
   float** pbufs[] = {&ctx->d_theta, &ctx->d_mom, &ctx->d_eps, &ctx->d_theta0, &ctx->d_lam, &ctx->d_lamld,
                      &ctx->d_grad};
   for (float** pb : pbufs) {
@@ -1031,27 +861,17 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
     CK(hipMemsetAsync(*pb, 0, p_off * sizeof(float), ctx->stream));
   }
   CK(dalloc(&ctx->d_stepbase, p_off));
-  for (float** qb : {&ctx->d_phi, &ctx->d_phi0, &ctx->d_mphi, &ctx->d_ephi, &ctx->d_gphi}) CK(dalloc(qb, q_off));
-  CK(dalloc(&ctx->d_ows, 2 * (int64_t)ctx->br.size()));
-  {  // parameter -> precision index (within the branch), for the joint update
-    std::vector<int32_t> pidx(p_off);
-    for (auto& h : ctx->br) {
-      const BranchDev& d = h.dev;
-      const bool ard = (h.prior == BANN_RIDGE_ARD || h.prior == BANN_LASSO_ARD);
-      for (int l = 0; l < h.L; ++l)
-        for (int k = 0; k < d.widths[l]; ++k)
-          for (int j = 0; j < d.win[l]; ++j)
-            pidx[d.p_off + d.woff[l] + (int64_t)k * d.win[l] + j] = d.qoff[l] + ((ard && l < h.L - 1) ? j : 0);
-      for (int l = 0; l < h.L - 1; ++l)
-        for (int k = 0; k < d.widths[l]; ++k) pidx[d.p_off + d.boff[l] + k] = d.qbias + l;
-    }
+  for (float** qb : {&ctx->d_phi, &ctx->d_phi0, &ctx->d_mphi, &ctx->d_ephi, &ctx->d_gphi}) CK(dalloc(qb, t.total_q));
+  CK(dalloc(&ctx->d_ows, 2 * nb));
+  {
+    const std::vector<int32_t> pidx = precision_index(ctx->br, p_off);
     CK(dalloc(&ctx->d_pidx, p_off));
     CK(hipMemcpy(ctx->d_pidx, pidx.data(), p_off * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  CK(dalloc(&ctx->d_part, part_off + ctx->solo_part_cap));
-  CK(hipMemsetAsync(ctx->d_part, 0, part_off * sizeof(float), ctx->stream));
-  CK(dalloc(&ctx->d_rss_part, nb * max_splits + ctx->solo_rss_cap));
-  CK(hipMemsetAsync(ctx->d_rss_part, 0, nb * max_splits * sizeof(double), ctx->stream));
+  CK(dalloc(&ctx->d_part, t.part_total + t.solo_part_cap));
+  CK(hipMemsetAsync(ctx->d_part, 0, t.part_total * sizeof(float), ctx->stream));
+  CK(dalloc(&ctx->d_rss_part, nb * t.max_splits + t.solo_rss_cap));
+  CK(hipMemsetAsync(ctx->d_rss_part, 0, nb * t.max_splits * sizeof(double), ctx->stream));
   CK(dalloc(&ctx->d_y, nb * n));
   CK(hipMemsetAsync(ctx->d_y, 0, nb * n * sizeof(float), ctx->stream));
   CK(dalloc(&ctx->d_pred, nb * n));
@@ -1059,6 +879,12 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   CK(dalloc(&ctx->d_pred0, nb * n));
   CK(dalloc(&ctx->d_delta, n));
   CK(dalloc(&ctx->d_delta_part, residual_delta_scratch_floats(n)));
+  return BANN_OK;
+}
+
+// the pinned host mirrors, the per-branch trajectory scalars and a per-call plan's scratch
+static int alloc_driver_scratch(bann_ctx* ctx, const LayoutTotals& t) {
+  const int64_t n = ctx->n, nb = (int64_t)ctx->br.size();
   CK(hipHostMalloc((void**)&ctx->h_status, nb * sizeof(int32_t), hipHostMallocDefault));
   {
     int64_t max_p = 1;
@@ -1067,7 +893,7 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   }
   CK(hipHostMalloc((void**)&ctx->h_delta, n * sizeof(float), hipHostMallocDefault));
   CK(hipMemsetAsync(ctx->d_pred0, 0, nb * n * sizeof(float), ctx->stream));
-  CK(dalloc(&ctx->d_scr, scr_off));
+  CK(dalloc(&ctx->d_scr, t.scr_floats));
   CK(dalloc(&ctx->d_eprec, nb));
   CK(dalloc(&ctx->d_upd_cnt, nb));
   CK(hipMemsetAsync(ctx->d_upd_cnt, 0, nb * sizeof(int32_t), ctx->stream));
@@ -1078,42 +904,36 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   CK(dalloc(&ctx->d_status, nb));
   CK(dalloc(&ctx->d_uturn, nb));
   CK(dalloc(&ctx->d_gen_scr, nb));
-  ctx->gxpre_cap = (int64_t)(3 * BANN_MAXL) * (n_gx + gx_ngroups + 2);
-  CK(dalloc(&ctx->d_gxpre_scr, ctx->gxpre_cap));
-  ctx->items_cap = items + ctx->solo_rss_cap;  // a solo plan has <= solo_rss_cap items
-  {  // a per-call plan's branch lists, fold jobs and work items: one device block, filled by
-     // ONE copy from a pinned stage (build_plan; was three copies per bann_hmc_step call)
-    auto al = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
-    ctx->plan_off_fold = al(2 * (int64_t)nb * (int64_t)sizeof(int32_t));
-    ctx->plan_off_items = ctx->plan_off_fold + al((int64_t)nb * (int64_t)sizeof(FoldJob));
-    ctx->plan_scr_bytes = ctx->plan_off_items + ctx->items_cap * (int64_t)sizeof(GradItem);
-    CK(hipMalloc((void**)&ctx->d_plan_scr, (size_t)ctx->plan_scr_bytes));
-    CK(hipHostMalloc((void**)&ctx->h_plan_stage, (size_t)ctx->plan_scr_bytes, hipHostMallocDefault));
-    CK(hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming));
-    ctx->d_list_scr = reinterpret_cast<int32_t*>(ctx->d_plan_scr);
-    ctx->d_fold_scr = reinterpret_cast<FoldJob*>(ctx->d_plan_scr + ctx->plan_off_fold);
-    ctx->d_items_scr = reinterpret_cast<GradItem*>(ctx->d_plan_scr + ctx->plan_off_items);
-  }
-  // every branch's tile image in ONE batched pack launch (no per-branch sync), the
-  // marker statistics in one gather, the precision-derived arrays in one copy each
-  std::vector<int32_t> allidx;
-  allidx.reserve(mk_off);
-  std::vector<PackJob> jobs;
+  CK(dalloc(&ctx->d_gxpre_scr, t.gxpre_cap));
+  // a per-call plan's branch lists, fold jobs and work items: one device block, filled by
+  // ONE copy from a pinned stage (upload_plan_scratch; was three copies per bann_hmc_step call)
+  CK(hipMalloc((void**)&ctx->d_plan_scr, (size_t)t.plan_scr_bytes));
+  CK(hipHostMalloc((void**)&ctx->h_plan_stage, (size_t)t.plan_scr_bytes, hipHostMallocDefault));
+  CK(hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming));
+  ctx->d_list_scr = reinterpret_cast<int32_t*>(ctx->d_plan_scr);
+  ctx->d_fold_scr = reinterpret_cast<FoldJob*>(ctx->d_plan_scr + t.plan_off_fold);
+  ctx->d_items_scr = reinterpret_cast<GradItem*>(ctx->d_plan_scr + t.plan_off_items);
+  return BANN_OK;
+}
+
+// every branch's tile image in ONE batched pack launch (no per-branch sync), the fi images
+// in another, the marker statistics in one gather
+static int pack_images(bann_ctx* ctx, const LayoutTotals& t, FinalizeStage& fs) {
+  const int64_t ntile = (t.nfrag + BANN_TILE_FRAGS - 1) / BANN_TILE_FRAGS;
+  fs.allidx.reserve(t.total_markers);
   for (auto& h : ctx->br) {
-    const int32_t base = (int32_t)allidx.size();
-    allidx.insert(allidx.end(), h.snp_idx.begin(), h.snp_idx.end());
+    const int32_t base = (int32_t)fs.allidx.size();
+    fs.allidx.insert(fs.allidx.end(), h.snp_idx.begin(), h.snp_idx.end());
     for (int c = 0; c < h.dev.nchunks; ++c)
-      jobs.push_back(PackJob{h.dev.x_off + 1024ll * c, 1024ll * h.dev.nchunks, base + 64 * c,
-                             std::min(64, h.m - 64 * c), tile_f3m1(h.dev.fused) ? 1 : 0});
+      fs.jobs.push_back(PackJob{h.dev.x_off + 1024ll * c, 1024ll * h.dev.nchunks, base + 64 * c,
+                                std::min(64, h.m - 64 * c), tile_f3m1(h.dev.fused) ? 1 : 0});
   }
-  int32_t* d_idx = nullptr;
-  PackJob* d_jobs = nullptr;
-  CK(dalloc(&d_idx, (int64_t)allidx.size()));
-  CK(dalloc(&d_jobs, (int64_t)jobs.size()));
-  CK(hipMemcpyAsync(d_idx, allidx.data(), allidx.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  CK(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, ctx->stream));
-  launch_pack_tiles(ctx->d_g, ctx->rowb, d_jobs, (int32_t)jobs.size(), d_idx, ntile, ctx->d_xu2, ctx->stream);
-  PackJob* d_fijobs = nullptr;
+  CK(dalloc(&fs.d_idx, (int64_t)fs.allidx.size()));
+  CK(dalloc(&fs.d_jobs, (int64_t)fs.jobs.size()));
+  CK(hipMemcpyAsync(fs.d_idx, fs.allidx.data(), fs.allidx.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                    ctx->stream));
+  CK(hipMemcpyAsync(fs.d_jobs, fs.jobs.data(), fs.jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, ctx->stream));
+  launch_pack_tiles(ctx->d_g, ctx->rowb, fs.d_jobs, (int32_t)fs.jobs.size(), fs.d_idx, ntile, ctx->d_xu2, ctx->stream);
   if (ctx->d_xi) {  // the fi images: one job per (branch, 256-marker segment)
     std::vector<PackJob> fj;
     int32_t base = 0;
@@ -1125,22 +945,30 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
                                std::min(256, h.m - 256 * sg)});
       base += h.m;
     }
-    CK(dalloc(&d_fijobs, (int64_t)fj.size()));
-    CK(hipMemcpyAsync(d_fijobs, fj.data(), fj.size() * sizeof(PackJob), hipMemcpyHostToDevice, ctx->stream));
-    launch_pack_fi(ctx->d_g, ctx->rowb, d_fijobs, (int32_t)fj.size(), d_idx, ntile, ctx->d_xi, ctx->stream);
+    CK(dalloc(&fs.d_fijobs, (int64_t)fj.size()));
+    CK(hipMemcpyAsync(fs.d_fijobs, fj.data(), fj.size() * sizeof(PackJob), hipMemcpyHostToDevice, ctx->stream));
+    launch_pack_fi(ctx->d_g, ctx->rowb, fs.d_fijobs, (int32_t)fj.size(), fs.d_idx, ntile, ctx->d_xi, ctx->stream);
     CK(hipStreamSynchronize(ctx->stream));  // fj goes out of scope
   }
-  launch_gather_stats(ctx->d_mu, ctx->d_sigma, d_idx, (int32_t)allidx.size(), ctx->d_mub, ctx->d_sigb, ctx->stream);
+  launch_gather_stats(ctx->d_mu, ctx->d_sigma, fs.d_idx, (int32_t)fs.allidx.size(), ctx->d_mub, ctx->d_sigb,
+                      ctx->stream);
   CK(hipGetLastError());
-  std::vector<BranchDev> descs;
-  std::vector<float> lam_all(p_off), lamld_all(p_off), eprec(nb, 1.f), lam, lamld;
+  return BANN_OK;
+}
+
+// the precision-derived arrays in one copy each, then the branch descriptors; frees the pack
+// launches' device arrays once the stream has drained
+static int upload_derived(bann_ctx* ctx, const LayoutTotals& t, FinalizeStage& fs) {
+  const int64_t nb = (int64_t)ctx->br.size(), p_off = t.total_p;
+  std::vector<float> lam_all(p_off), lamld_all(p_off), lam, lamld;
   std::vector<double> sbase_all(p_off), sbase;
+  fs.eprec.assign(nb, 1.f);
   for (size_t b = 0; b < ctx->br.size(); ++b) {
     BranchHost& h = ctx->br[b];
-    descs.push_back(h.dev);
+    fs.descs.push_back(h.dev);
     float ep = 1.f;
     expand_precisions(h, lam, lamld, ep);
-    eprec[b] = ep;
+    fs.eprec[b] = ep;
     step_bases(h, sbase);
     std::copy(lam.begin(), lam.end(), lam_all.begin() + h.dev.p_off);
     std::copy(lamld.begin(), lamld.end(), lamld_all.begin() + h.dev.p_off);
@@ -1150,19 +978,55 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   CK(hipMemcpyAsync(ctx->d_lamld, lamld_all.data(), p_off * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   CK(hipMemcpyAsync(ctx->d_stepbase, sbase_all.data(), p_off * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   CK(hipStreamSynchronize(ctx->stream));  // host vectors go out of scope
-  dfree(d_idx);
-  dfree(d_jobs);
-  dfree(d_fijobs);
+  dfree(fs.d_idx);
+  dfree(fs.d_jobs);
+  dfree(fs.d_fijobs);
   CK(dalloc(&ctx->d_br, nb));
-  CK(hipMemcpyAsync(ctx->d_br, descs.data(), nb * sizeof(BranchDev), hipMemcpyHostToDevice, ctx->stream));
-  CK(hipMemcpyAsync(ctx->d_eprec, eprec.data(), nb * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  if (opt.stamps) {
+  CK(hipMemcpyAsync(ctx->d_br, fs.descs.data(), nb * sizeof(BranchDev), hipMemcpyHostToDevice, ctx->stream));
+  CK(hipMemcpyAsync(ctx->d_eprec, fs.eprec.data(), nb * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->opt.stamps) {
     CK(hipMalloc((void**)&ctx->d_dbg, 16 * sizeof(unsigned long long)));
     CK(hipMemsetAsync(ctx->d_dbg, 0, 16 * sizeof(unsigned long long), ctx->stream));
   }
+  return BANN_OK;
+}
+
+extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
+  if (!ctx) return BANN_E_ARG;
+  if (ctx->finalized) return fail(ctx, BANN_E_STATE, "already finalized");
+  if (!ctx->d_g) return fail(ctx, BANN_E_STATE, "no genotypes uploaded");
+  if (ctx->br.empty()) return fail(ctx, BANN_E_STATE, "no branches");
+  CK(hipSetDevice(ctx->device));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0)
+    cus = 256;
+  ctx->cus = cus;
+  const LayoutTotals t =
+      plan_layout(ctx->n, ctx->M, cus, gx_scratch_budget(ctx->opt), ctx->fused_enabled, ctx->opt, ctx->br);
+  if (t.err) return fail(ctx, t.err, t.msg);
+  ctx->nfrag = t.nfrag;
+  ctx->max_splits = t.max_splits;
+  ctx->solo_threshold = t.solo_threshold;
+  ctx->solo_rss_cap = t.solo_rss_cap;
+  ctx->solo_part_cap = t.solo_part_cap;
+  ctx->part_total = t.part_total;
+  ctx->packed_bytes = t.tile_bytes;
+  ctx->total_p = t.total_p;
+  ctx->total_q = t.total_q;
+  ctx->gxpre_cap = t.gxpre_cap;
+  ctx->items_cap = t.items_cap;
+  ctx->plan_off_fold = t.plan_off_fold;
+  ctx->plan_off_items = t.plan_off_items;
+  ctx->plan_scr_bytes = t.plan_scr_bytes;
+  FinalizeStage fs;  // outlives every asynchronous copy below
+  int rc = alloc_branch_state(ctx, t);
+  if (!rc) rc = alloc_driver_scratch(ctx, t);
+  if (!rc) rc = pack_images(ctx, t, fs);
+  if (!rc) rc = upload_derived(ctx, t, fs);
+  if (rc) return rc;
   ctx->finalized = true;
   ctx->pred_ok.assign(ctx->br.size(), 0);
-  int rc = ensure_htrace(ctx, 1);
+  rc = ensure_htrace(ctx, 1);
   if (rc) return rc;
   rc = net_buffers_init(ctx);  // the network sampler allocates nothing inside its trajectories
   if (rc) return rc;

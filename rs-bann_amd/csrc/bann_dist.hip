@@ -240,7 +240,7 @@ int net_buffers_init(bann_ctx* ctx) {
   if (!ctx->d_gsum && ctx->opt.net_gsum) {  // one row per (at least) 8 fx branches of 8 chunks and one (L, act)
     std::vector<std::pair<int64_t, int32_t>> cls;  // ((L, act), count)
     for (const auto& h : ctx->br)
-      if (h.dev.fused == 1 && h.dev.nchunks == 8) {
+      if (h.dev.fused == PATH_FX && h.dev.nchunks == 8) {
         const int64_t key = (int64_t)h.L * 64 + h.act;
         bool found = false;
         for (auto& c : cls)
@@ -278,14 +278,16 @@ extern "C" int bann_network_step_rule_info(const bann_ctx* ctx, double* out4) {
 // k_forward_gsum's work items for a persistent network plan: usable when every branch of the
 // plan is an fx branch of exactly 8 chunks (the full8 groups), L <= 4.  An item takes up to
 // 8 R of a launch group's branches (plan order) over one range of T <= forward_gsum_max_tiles()
-// tiles, and writes one row; (R, number of ranges) minimise rounds (one workgroup per CU) x
-// R x (T + 2), ties going to the larger R (fewer rows).  BANN_NET_GSUM_R forces R (tests).
+// tiles, and writes one row; (R, number of ranges): choose_gsum (finalize_layout.h), one workgroup
+// per CU.  BANN_NET_GSUM_R forces R (tests).  Where it finds no candidate (n beyond 512 ranges of
+// the most tiles, or a forced R above 32) the plan has no group rows and the network step takes
+// the per-branch forward.
 int build_net_groups(bann_ctx* ctx, Plan& p) {
   p.nsum_built = true;
   p.nsum_rows = 0;
   if (!ctx->d_gsum || !p.gx.empty() || p.groups.empty()) return BANN_OK;
   for (const auto& g : p.groups)
-    if (g.kind != 1 || !g.full || g.L < 2 || g.L > 4) return BANN_OK;
+    if (g.kind != PATH_FX || !g.full || g.L < 2 || g.L > 4) return BANN_OK;
   const int64_t ntile = ((int64_t)ctx->nfrag + BANN_TILE_FRAGS - 1) / BANN_TILE_FRAGS;
   const int64_t tmax = forward_gsum_max_tiles();
   const int64_t slots = ctx->cus;
@@ -296,21 +298,10 @@ int build_net_groups(bann_ctx* ctx, Plan& p) {
     for (const auto& it : g.items)
       if (brs.empty() || brs.back() != it.branch) brs.push_back(it.branch);
     const int64_t nb = (int64_t)brs.size();
-    int64_t best = -1, r_best = 1, k_best = 1;
-    for (int64_t R = 1; R <= 32; ++R) {
-      if (force_r && R != force_r) continue;
-      const int64_t ng = (nb + 8 * R - 1) / (8 * R);
-      for (int64_t k = (ntile + tmax - 1) / tmax; k <= std::min<int64_t>(ntile, 512); ++k) {
-        const int64_t T = (ntile + k - 1) / k;
-        const int64_t cost = ((ng * k + slots - 1) / slots) * R * (T + 2);
-        if (best < 0 || cost <= best) best = cost, r_best = R, k_best = k;
-      }
-    }
-    const int64_t per = 8 * r_best, ng = (nb + per - 1) / per;
-    if (row + ng > ctx->gsum_cap) {  // cannot happen: the cap counts every 8-chunk fx branch in 8s
-      p.nsum_rows = 0;
-      return BANN_OK;
-    }
+    const GsumChoice c = choose_gsum(ntile, nb, slots, tmax, force_r);
+    if (!c.found) return BANN_OK;  // an item would span more than tmax tiles: the per-branch forward
+    const int64_t k_best = c.k, per = 8 * c.R, ng = (nb + per - 1) / per;
+    if (row + ng > ctx->gsum_cap) return BANN_OK;  // cannot happen: the cap counts every 8-chunk fx branch in 8s
     g.nitems.clear();
     for (int64_t gi = 0; gi < ng; ++gi)
       for (int64_t s = 0; s < k_best; ++s) {
@@ -469,7 +460,7 @@ extern "C" int bann_network_hmc_step(bann_ctx* ctx, const float* y, float bias, 
   ctx->st.net_le = lambda_e;
   // fx-only plans: the gradient kernel reads e itself (DevState::nete), no per-branch targets
   bool fx_only = p.gx.empty();
-  for (const auto& g : p.groups) fx_only = fx_only && g.kind == 1;
+  for (const auto& g : p.groups) fx_only = fx_only && g.kind == PATH_FX;
   fx_only = fx_only && ctx->opt.net_err;  // BANN_NET_ERR=0: per-branch targets for every kind (diagnostics)
   ctx->st.nete = fx_only ? ctx->d_netsum : nullptr;
   // group sums (k_forward_gsum): every step's forward but the last writes one row per group of

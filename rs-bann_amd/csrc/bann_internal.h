@@ -17,6 +17,9 @@
 
 enum { MODE_GRAD = 0, MODE_INIT = 1, MODE_STEP = 2, MODE_LAST = 3, MODE_PROFILE = 4, MODE_RESTORE = 5 };
 enum { ST_RUNNING = -1, ST_ACCEPTED = 0, ST_REJECTED = 1, ST_REJECTED_EARLY = 2 };
+// kernel path of a branch (BranchDev::fused, LaunchGroup::kind, bann_branch_kernel_path): gx = layered
+// MFMA GEMMs; fx, fxl = every width <= 4, up to 8 / 64 marker chunks; wx = one wide hidden layer
+enum { PATH_GX = 0, PATH_FX = 1, PATH_WX = 2, PATH_FXL = 3 };
 
 // Per-branch descriptor (device resident, one per branch).
 struct BranchDev {
@@ -35,7 +38,7 @@ struct BranchDev {
   int32_t prior;      // bann_prior
   int32_t P;          // num params
   int32_t nsplits;    // row splits (partial slabs)
-  int32_t fused;      // kernel path: 1 = fx, 3 = fxl (widths <= 4), 2 = wide (wx), 0 = gx (layered MFMA GEMMs)
+  int32_t fused;      // kernel path: PATH_*
   int32_t widths[BANN_MAXL];  // out width of each layer (last = 1)
   int32_t win[BANN_MAXL];     // in width of each layer (win[0] = m)
   int32_t woff[BANN_MAXL];    // param_vec offset of W_l
@@ -162,7 +165,7 @@ struct PackJob {
 };
 // the fx / fxl / fxh kernels read their tile images with field 3 stored as code - 1
 // (kernels_fx.hip header); the wide and layered kernels read plain codes
-__host__ __device__ inline bool tile_f3m1(int fused) { return fused == 1 || fused == 3; }
+__host__ __device__ inline bool tile_f3m1(int path) { return path == PATH_FX || path == PATH_FXL; }
 // genotype image: 2-bit variant-major rows of rowb = ceil(n/64)*16 bytes (kernels_data.hip header)
 void launch_synthetic_genotypes(uint8_t* raw, int64_t rowb, float* mu, float* sigma, int64_t n, int64_t M,
                                 uint64_t seed, hipStream_t s);
@@ -250,8 +253,6 @@ void launch_pack_fi(const uint8_t* raw, int64_t rowb, const PackJob* jobs, int32
                     int64_t ntile, uint8_t* dst, hipStream_t s);
 void launch_fused_grad_fxl(const DevState& st, const GradItem* items, int32_t nitems, int32_t L, int32_t act,
                            int32_t nw, int32_t cpw, int full, int write_pred, int head, hipStream_t s);
-int fxl_lds_bytes(int nw, int nl, int cpw);
-int fxl_cpw(int nchunks, int force);  // marker chunks per fxl wave: 4 up to 32 chunks, else 8 (force = 8: always 8)
 void launch_step_sizes(const DevState& st, const double* base, const int32_t* branches, int32_t nb, int32_t max_p,
                        int izmailov, float c, int32_t L, hipStream_t s);
 void launch_restore_pred(const DevState& st, const int32_t* branches, int32_t nb, hipStream_t s);

@@ -10,23 +10,11 @@
 #include "../../include/bann.h"
 #include "bann_internal.h"
 #include "env_options.h"
-
-struct BranchHost {
-  std::vector<int32_t> snp_idx;
-  std::vector<int32_t> widths;
-  int32_t m = 0, L = 0, act = 0, prior = 0;
-  int32_t P = 0, nprec = 0;
-  std::vector<float> prec;  // precision_vec order
-  float ows_reg_sum = 0.f;  // output-weight summary stat of the OTHER branches (joint HMC)
-  float ows_num = -1.f;     // output-weight count of the network (< 0: this branch's own)
-  int32_t gx_group = -1;    // gx path: scratch group (branches of one group share no scratch)
-  int32_t solo_items = 1;   // fused path: work items of the branch in a solo-mode plan (~1 tile per wave)
-  BranchDev dev{};
-};
+#include "finalize_layout.h"  // BranchHost
 
 // one packed gradient launch: every work item of one kernel instantiation
 struct LaunchGroup {
-  int32_t kind = 0;  // BranchDev::fused of its branches: 1 fx, 3 fxl, 2 wx
+  int32_t kind = 0;  // BranchDev::fused of its branches: PATH_FX, PATH_FXL or PATH_WX
   int32_t L = 0, act = 0, nw = 1, full = 0;
   int32_t cpw = 8;      // fxl: marker chunks per wave (fxl_cpw)
   int32_t head = 0;     // fxl: the head-wave kernel fxh where its shape allows (EnvOptions::fxl_head)
@@ -89,7 +77,8 @@ struct bann_ctx {
   std::vector<BranchHost> br;
   bool finalized = false;
   bool fused_enabled = true;
-  bool wide_bf16 = false;  // wx kernel: hidden GEMMs on bf16 MFMA (opt-in, reduced precision)
+  // wx kernel: hidden GEMMs on bf16 MFMA (opt-in, reduced precision; bann_set_hidden_gemm_bf16)
+  bool wide_bf16 = false;
   // the BANN_* switches, read once as bann_ctx_create constructs the context and fixed for its life
   const EnvOptions opt = read_env_options();
   int32_t nfrag = 0, max_splits = 1;

@@ -10,7 +10,7 @@ struct EnvOptions {
   bool gx_exact = false;     // BANN_GX_EXACT=1: every gx phase on the exact-f32 MFMA path, eager head
   bool net_err = true;       // BANN_NET_ERR=0: per-branch targets for every kernel kind (diagnostics)
   bool net_gsum = true;      // BANN_NET_GSUM=0: per-branch output rows in every network step (A/B)
-  int32_t net_gsum_r = 0;    // BANN_NET_GSUM_R: forces build_net_groups' R (tests), >= 1; 0: its own choice
+  int32_t net_gsum_r = 0;    // BANN_NET_GSUM_R: forces build_net_groups' R (tests), 1..32 (above: no group rows); 0: its own choice
   bool fwd_fi = false;       // BANN_FWD_FI=1: individual-major fi images and forward for the fx branches
   int32_t fi_waves_per_simd = 3;  // BANN_FI_WAVES_PER_SIMD: the fi forward's grid
   bool fxl_head = true;      // BANN_FXL_HEAD=0: fxl groups of 17..32 chunks off the head-wave kernel

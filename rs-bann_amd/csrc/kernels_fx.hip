@@ -43,12 +43,12 @@
 
 #include "activations.h"
 #include "bann_internal.h"
+#include "fx_shapes.h"
 #include "kernel_util.h"
 #include "update_core.h"
 
 #define FX_WAVES 4        // waves per workgroup (one work item, tiles interleaved)
 #define FX_SLOT 8192      // one tile image at <= 8 chunks (512 markers x 16 B)
-#define FX_DROW 256       // delta0 digit image: 16 rows x 16 B per K group (read twice per tile)
 
 // Profiling builds only (tools/build_ab.sh <tag> "-DFX_STAMPS=1" / "-DFX_ABL=<bits>"); both 0 in the
 // product, where they generate no code.  FX_STAMPS: per-phase shader-cycle sums of k_fused_grad_fx
@@ -1296,7 +1296,7 @@ void launch_forward_gsum(const DevState& st, const NetGroupItem* items, int32_t 
 // 4-wave workgroups per CU), so the W0/sigma digit operand is read from L2 into
 // registers two chunks ahead with counted loads instead of an LDS image.
 // ===========================================================================
-#define FXL_MAXW 8
+// FXL_MAXW (waves per workgroup), fxl_lds_bytes and fxl_cpw: fx_shapes.h
 // k_fused_grad_fxh (below)
 #define FXH_CPW 5   // chunks per compute wave (at most)
 #define FXH_MAXC 7  // compute waves (+ the head wave: 8 waves)
@@ -1322,11 +1322,6 @@ __device__ __forceinline__ void vm_wait_tie(int k, v4i& d) {
     case 2: asm volatile("s_waitcnt vmcnt(2)" : "+v"(d)::"memory"); break;
     default: asm volatile("s_waitcnt vmcnt(3)" : "+v"(d)::"memory"); break;
   }
-}
-
-int fxl_lds_bytes(int nw, int nl, int cpw) {
-  const int ns = 8 + (nl - 2) * 20;
-  return nw * (2 * cpw * 1024 + 4 * FX_DROW + 2 * 64 * 16) + 2 * 64 * 4 + nl * 20 * 4 + ns * 4;
 }
 
 // CPW: chunks per wave.  8 (branches of 33 .. 64 chunks): the wave's W0 digit
@@ -1779,10 +1774,6 @@ static void launch_fxl_nl(const DevState& st, const GradItem* items, int32_t nit
     default: FXL_GO(4); break;
   }
 #undef FXL_GO
-}
-
-int fxl_cpw(int nchunks, int force) {  // force = 8 (EnvOptions::fxl_cpw): the old scheme (A/B)
-  return (nchunks <= 4 * FXL_MAXW && force != 8) ? 4 : 8;
 }
 
 // nw waves per workgroup (= ceil(chunks / cpw) of every branch of the launch);

@@ -38,7 +38,7 @@ __device__ void refresh_fused_const(const DevState& st, int b, const BranchDev& 
   const float* mu = st.mu + bd.mk_off;
   const float* sg = st.sigma + bd.mk_off;
   const int m = bd.m, w0 = bd.widths[0];
-  const int NB = bd.fused == 2 ? 8 : 1;  // column blocks of 4 in the digit image (wide kernel: 8)
+  const int NB = bd.fused == PATH_WX ? 8 : 1;  // column blocks of 4 in the digit image (wide kernel: 8)
   uint8_t* dig = const_cast<uint8_t*>(st.dig) + bd.dig_off;
   const int wv = threadIdx.x >> 6;
   // four columns per pass: their max |W0/sigma| and mu . (W0/sigma) in one
@@ -145,13 +145,14 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 5
   if (prof) mode = MODE_STEP;
   if (mode == MODE_RESTORE) {  // back to theta_0 (a rejected network trajectory)
     for (int i = threadIdx.x; i < P; i += NT) st.theta[base + i] = st.theta0[base + i];
-    if (bd.fused) {
+    if (bd.fused != PATH_GX) {
       __syncthreads();
       refresh_fused_const<NT>(st, b, bd);
     }
     return;
   }
-  if ((((bd.fused == 1 || bd.fused == 3) && bd.widths[0] <= 4) || (bd.fused == 2 && bd.widths[0] <= 32)) &&
+  if ((((bd.fused == PATH_FX || bd.fused == PATH_FXL) && bd.widths[0] <= 4) ||
+       (bd.fused == PATH_WX && bd.widths[0] <= 32)) &&
       P <= upd_cap<NT>() * NT && bd.m <= MPT * NT) {
     __shared__ float s_th[upd_cap<NT>() * NT];
     update_small<NT, MPT>(st, b, bd, mode, prof, step, redd, s_th);  // checks the status itself
@@ -261,7 +262,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 5
       }
     }
   }
-  if (bd.fused) {
+  if (bd.fused != PATH_GX) {
     __syncthreads();
     __threadfence_block();
     refresh_fused_const<NT>(st, b, bd);
@@ -284,7 +285,7 @@ bool update_is_large(const BranchDev& d) { return d.P > UPD_CAP * UPD_THREADS ||
 __global__ void __launch_bounds__(UPD_THREADS) k_fused_const(DevState st, const int32_t* __restrict__ blist) {
   const int b = blist[blockIdx.x];
   const BranchDev bd = st.br[b];
-  if (bd.fused) refresh_fused_const<UPD_THREADS>(st, b, bd);
+  if (bd.fused != PATH_GX) refresh_fused_const<UPD_THREADS>(st, b, bd);
 }
 
 void launch_fused_const(const DevState& st, const int32_t* branches, int32_t nb, hipStream_t s) {
@@ -828,7 +829,7 @@ __global__ void __launch_bounds__(UPD_J) k_update_joint(DevState st, const int32
     for (int i = t; i < P; i += UPD_J) st.theta[base + i] = st.theta0[base + i];
     for (int q = t; q < nq; q += UPD_J) phi[q] = st.phi0[qb + q];
   }
-  if (bd.fused && act != 2) {
+  if (bd.fused != PATH_GX && act != 2) {
     __syncthreads();
     refresh_fused_const<UPD_J>(st, b, bd);
   }

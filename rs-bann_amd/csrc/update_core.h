@@ -332,7 +332,7 @@ __device__ void update_small(const DevState& st, int b, const BranchDev& bd, int
   // four columns per pass (wide branches: eight passes, digit image of 8 column blocks) ----
   const float* W0 = s_th + bd.woff[0];
   const float* b0 = s_th + bd.boff[0];
-  const int NB = bd.fused == 2 ? 8 : 1;
+  const int NB = bd.fused == PATH_WX ? 8 : 1;
   uint8_t* dig = const_cast<uint8_t*>(st.dig) + bd.dig_off;
   __shared__ float s_mx[4][NV_T / 64];
   __shared__ double s_cs[4][NV_T / 64];
