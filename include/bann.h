@@ -171,6 +171,26 @@ int bann_predict(bann_ctx* ctx, int32_t b, float* pred_out);
  * per-branch loop of net.rs:272-282 when the residual is rebuilt); pred_out is
  * nb x n, row i = branch branches[i]. */
 int bann_predict_many(bann_ctx* ctx, const int32_t* branches, int32_t nb, float* pred_out);
+/* ---------------- model slots: a chain of saved models from one genotype pass ----------------
+ * A bank of num_models parameter sets beside the live one (rs-bann predict, rs-bann.rs:276-312:
+ * one prediction row per saved model).  Slot k holds its own parameters per branch and one
+ * output bias; no slot call changes the live parameters, predictions, targets, momenta or step
+ * sizes.  BANN_E_STATE before bann_finalize and inside a leapfrog session, BANN_E_ARG for a
+ * slot or branch out of range.  bann_models_reserve(0) frees the bank; reserving again
+ * empties every slot. */
+int bann_models_reserve(bann_ctx* ctx, int32_t num_models);
+int bann_models_capacity(const bann_ctx* ctx);
+/* models served by one pass over the genotypes (a chain of any length takes several passes) */
+int bann_models_pass_width(void);
+int bann_models_set_params(bann_ctx* ctx, int32_t k, int32_t b, const float* param_vec);
+int bann_models_set_bias(bann_ctx* ctx, int32_t k, float bias);
+/* y_hat_out[nk][n]: row j = Net::predict (net.rs:545-559) of slot k0 + j, 0 + bias then += f_b in
+ * branch order in f32.  mean_out[n] / var_out[n] (either may be NULL): mean and sample variance
+ * (nk - 1; 0 for nk = 1) over the nk rows, accumulated in f64.  BANN_E_STATE if a slot of the
+ * range has a branch whose parameters were never set. */
+int bann_models_predict(bann_ctx* ctx, int32_t k0, int32_t nk, float* y_hat_out, float* mean_out, float* var_out);
+/* the per-branch rows f_b of slot k: pred_out is nb x n, row i = branch branches[i] (bann_predict_many) */
+int bann_models_branch_predictions(bann_ctx* ctx, int32_t k, const int32_t* branches, int32_t nb, float* pred_out);
 /* rss (branch_sampler.rs:905-909) against the branch target */
 int bann_rss(bann_ctx* ctx, int32_t b, double* rss_out);
 /* log_density_gradient (branch_sampler.rs:380-391: backpropagate 813-875 +

@@ -151,6 +151,15 @@ int bann_net_perturb(bann_net* net, int32_t has_params, float params_by, int32_t
  * widths) -- e.g. a test cohort -- or NULL for the net's own context.  The net's
  * current parameters are loaded into ctx first. */
 int bann_net_predict(bann_net* net, bann_ctx* ctx, float* y_hat_out);
+/* rs-bann predict (rs-bann.rs:276-312): y_hat_out[num_models][n], row j = Net::predict of the
+ * model file paths[j] on the cohort of ctx (NULL: the net's own).  The files are loaded into
+ * the context's model slots (bann_models_*), which this call reserves in bounded chunks and
+ * frees again (slots the caller had reserved are gone): the net's own state and the context's
+ * live parameters are unchanged.  mean_out / var_out as in
+ * bann_models_predict, over all num_models rows.  A file that does not match the net fails
+ * the call before anything is written to y_hat_out. */
+int bann_net_predict_models(bann_net* net, bann_ctx* ctx, const char* const* paths, int32_t num_models,
+                            float* y_hat_out, float* mean_out, float* var_out);
 /* Net::rss / Net::mse (net.rs:637-646) on the cohort of ctx (NULL: the net's own)
  * against y[n]: sum (y - y_hat)^2 with y_hat of bann_net_predict; mse = rss / n */
 int bann_net_rss(bann_net* net, bann_ctx* ctx, const float* y, int64_t n, double* rss_out);

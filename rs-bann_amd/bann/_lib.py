@@ -160,6 +160,14 @@ SIGNATURES = {
     "bann_branch_get_step_sizes": (C.c_int, [_P, C.c_int32, _P]),
     "bann_predict_many": (C.c_int, [_P, _P, C.c_int32, _P]),
     "bann_synchronize": (C.c_int, [_P]),
+    # model slots: a chain of saved models from one genotype pass
+    "bann_models_reserve": (C.c_int, [_P, _i32]),
+    "bann_models_capacity": (C.c_int, [_P]),
+    "bann_models_pass_width": (C.c_int, []),
+    "bann_models_set_params": (C.c_int, [_P, _i32, _i32, _pf32]),
+    "bann_models_set_bias": (C.c_int, [_P, _i32, _f32]),
+    "bann_models_predict": (C.c_int, [_P, _i32, _i32, _pf32, _pf32, _pf32]),
+    "bann_models_branch_predictions": (C.c_int, [_P, _i32, _pi32, _i32, _pf32]),
     "bann_profile_session": (C.c_int, [_P, _i32, _pf32, _pf32]),
     "bann_branch_kernel_path": (C.c_int, [_P, _i32]),
     "bann_set_fused_enabled": (C.c_int, [_P, _i32]),
@@ -174,6 +182,7 @@ SIGNATURES = {
     "bann_net_train_single_branch": (C.c_int, [_P, _pf32, _i64, C.POINTER(McmcCfg), C.c_char_p]),
     "bann_net_perturb": (C.c_int, [_P, _i32, _f32, _i32, _f32]),
     "bann_net_predict": (C.c_int, [_P, _P, _pf32]),
+    "bann_net_predict_models": (C.c_int, [_P, _P, C.POINTER(C.c_char_p), _i32, _pf32, _pf32, _pf32]),
     "bann_net_rss": (C.c_int, [_P, _P, _pf32, _i64, _pf64]),
     "bann_net_gradient": (C.c_int, [_P, _P, _pf32, _i64, _pf32]),
     "bann_net_branch_r2s": (C.c_int, [_P, _P, _pf32, _i64, _pf32]),

@@ -198,6 +198,47 @@ class BannContext:
         self._check(self._lib.bann_predict_many(self._h, _ptr(bl, C.c_int32), bl.size, _ptr(out, C.c_float)))
         return out
 
+    # ---------------------------------------------------------- model slots
+    def models_reserve(self, num_models: int):
+        """a bank of num_models parameter sets beside the live one (0 frees it); empties every slot."""
+        self._check(self._lib.bann_models_reserve(self._h, int(num_models)))
+
+    def models_capacity(self) -> int:
+        return int(self._lib.bann_models_capacity(self._h))
+
+    def models_pass_width(self) -> int:
+        """models served by one pass over the genotypes."""
+        return int(self._lib.bann_models_pass_width())
+
+    def models_set_params(self, k: int, b: int, param_vec):
+        v = _f32(param_vec)
+        if 0 <= b < len(self._branches):
+            assert v.size == self.num_params(b), "param_vec size"
+        self._check(self._lib.bann_models_set_params(self._h, int(k), int(b), _ptr(v, C.c_float)))
+
+    def models_set_bias(self, k: int, bias: float):
+        self._check(self._lib.bann_models_set_bias(self._h, int(k), float(bias)))
+
+    def models_predict(self, k0: int = 0, nk: Optional[int] = None, moments: bool = False):
+        """(nk, n) rows, row j = Net::predict of slot k0 + j (bias + sum_b f_b, f32, branch order); the
+        live parameters and predictions are untouched.  moments: also (mean, var) over the rows (sample variance)."""
+        nk = self.models_capacity() - k0 if nk is None else int(nk)
+        out = np.zeros((max(nk, 0), self.n), np.float32)
+        mean = np.zeros(self.n, np.float32) if moments else None
+        var = np.zeros(self.n, np.float32) if moments else None
+        self._check(self._lib.bann_models_predict(self._h, int(k0), nk, _ptr(out, C.c_float),
+                                                  _ptr(mean, C.c_float) if moments else None,
+                                                  _ptr(var, C.c_float) if moments else None))
+        return (out, mean, var) if moments else out
+
+    def models_branch_predictions(self, k: int, branches) -> np.ndarray:
+        """(len(branches), n) per-branch rows f_b of slot k, laid out as predict_many."""
+        bl = np.ascontiguousarray(branches, dtype=np.int32)
+        out = np.zeros((bl.size, self.n), np.float32)
+        self._check(self._lib.bann_models_branch_predictions(self._h, int(k), _ptr(bl, C.c_int32), bl.size,
+                                                             _ptr(out, C.c_float)))
+        return out
+
     def rss(self, b: int) -> float:
         r = C.c_double()
         self._check(self._lib.bann_rss(self._h, b, C.byref(r)))

@@ -5,10 +5,13 @@
   read_grouping       ExternalGrouping::from_file (group/external.rs:15-60)
   uniform_grouping    UniformGrouping::new (group/uniform.rs:11-23)
   read_phen/write_phen Phenotypes::from_file / to_file (data/phenotypes.rs:28-36)
+  list_model_files / write_predictions_csv   the model listing and the CSV records of
+                      rs-bann predict (rs-bann.rs:288-311); pure Python
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import List
 
 import numpy as np
@@ -62,3 +65,28 @@ def write_phen(path: str, y) -> None:
     ya = np.ascontiguousarray(y, dtype=np.float32)
     _chk(load_library().bann_phen_write(path.encode(), ya.ctypes.data_as(C.POINTER(C.c_float)), ya.size),
          f"bann_phen_write({path})")
+
+
+def list_model_files(model_dir: str) -> List[str]:
+    """every regular file of model_dir, sorted as Rust sorts the paths (byte order), subdirectories
+    skipped (rs-bann.rs:291-297)."""
+    d = os.fsencode(model_dir)
+    names = sorted(e for e in os.listdir(d) if os.path.isfile(os.path.join(d, e)))
+    return [os.fsdecode(os.path.join(d, e)) for e in names]
+
+
+def format_f32(x) -> str:
+    """Rust's f32::to_string: the shortest digits that round-trip, never an exponent; NaN, inf, -inf."""
+    v = np.float32(x)
+    if np.isnan(v):
+        return "NaN"
+    if np.isinf(v):
+        return "inf" if v > 0 else "-inf"
+    return np.format_float_positional(v, unique=True, trim="-")
+
+
+def write_predictions_csv(file, rows) -> None:
+    """one record per model (row), comma separated, newline terminated, values as f32::to_string
+    (rs-bann.rs:308-309).  file: a text file object."""
+    for row in np.atleast_2d(np.asarray(rows, dtype=np.float32)):
+        file.write(",".join(format_f32(v) for v in row) + "\n")

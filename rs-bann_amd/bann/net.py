@@ -123,6 +123,28 @@ class Net:
     def _ctxh(self, ctx):
         return ctx._h if ctx is not None else None
 
+    def predict_models(self, paths, ctx=None, moments: bool = False):
+        """rs-bann predict (rs-bann.rs:276-312): (len(paths), n) rows, row j = Net::predict of the model
+        file paths[j] on ctx's cohort (default: the training context), through the context's model
+        slots -- this net and the context's live parameters are unchanged.  moments: also (mean, var)
+        over the rows.  A file that does not match the net raises before any row is written."""
+        c = ctx if ctx is not None else self._ctx
+        paths = [str(p) for p in paths]
+        arr = (C.c_char_p * max(len(paths), 1))(*[p.encode() for p in paths])
+        out = np.zeros((len(paths), c.n), np.float32)
+        mean = np.zeros(c.n, np.float32) if moments else None
+        var = np.zeros(c.n, np.float32) if moments else None
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.bann_net_predict_models(self._h, self._ctxh(ctx), arr, len(paths), out.ctypes.data_as(fp),
+                                                      mean.ctypes.data_as(fp) if moments else None,
+                                                      var.ctypes.data_as(fp) if moments else None))
+        return (out, mean, var) if moments else out
+
+    def predict_dir(self, model_dir: str, ctx=None, moments: bool = False):
+        """predict_models over every regular file of model_dir in sorted order (rs-bann.rs:291-297)."""
+        from .io import list_model_files
+        return self.predict_models(list_model_files(model_dir), ctx=ctx, moments=moments)
+
     def rss(self, y, ctx=None) -> float:
         """Net::rss (net.rs:637-642): sum (y - predict)^2 on ctx's cohort (default: training)."""
         v = np.ascontiguousarray(y, dtype=np.float32)

@@ -41,6 +41,7 @@ void free_plan(Plan& p) {
 }
 
 void clear_graphs(bann_ctx* ctx);
+void models_release(bann_ctx* ctx);  // the model slots (end of this file)
 
 void refresh_state(bann_ctx* ctx) {
   clear_graphs(ctx);  // captured kernel arguments hold the old state
@@ -574,6 +575,7 @@ extern "C" int bann_ctx_destroy(bann_ctx* ctx) {
     (void)hipFree(ctx->d_dbg);
   }
   free_plan(ctx->lf);
+  models_release(ctx);
   void* bufs[] = {ctx->d_g, ctx->d_mu, ctx->d_sigma, ctx->d_br, ctx->d_xu2, ctx->d_xi, ctx->d_dig, ctx->d_fc, ctx->d_mub,
                   ctx->d_sigb, ctx->d_theta, ctx->d_mom, ctx->d_eps, ctx->d_theta0, ctx->d_lam, ctx->d_lamld,
                   ctx->d_grad, ctx->d_part, ctx->d_rss_part, ctx->d_y, ctx->d_pred, ctx->d_pred0, ctx->d_scr, ctx->d_eprec,
@@ -2168,5 +2170,206 @@ extern "C" int bann_profile_session(bann_ctx* ctx, int32_t iters, float* grad_ms
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   (void)hipEventDestroy(e2);
+  return BANN_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Model slots: a bank of parameter sets beside the live one, for predicting a chain of
+// saved models from one genotype pass (rs-bann predict, rs-bann.rs:276-312).  A slot owns
+// its theta, its W0 / sigma digit image and its fused constants; every slot kernel runs on
+// a DevState copy whose theta / dig / fc point at the slot and whose prediction rows point
+// at the pass scratch, so the live state (theta, dig, fc, pred, pred0, pred_ok, targets,
+// momenta, step sizes) is never written.  The partial-gradient slabs, rss partials and the
+// gx scratch, which every evaluation rewrites, serve the non-fx paths as scratch.
+// ---------------------------------------------------------------------------
+static void models_free(bann_ctx* ctx) {
+  void* bufs[] = {ctx->d_ms_theta, ctx->d_ms_dig, ctx->d_ms_fc, ctx->d_ms_rows, ctx->d_ms_yhat, ctx->d_ms_mom};
+  for (void* p : bufs) dfree(p);
+  ctx->d_ms_theta = nullptr;
+  ctx->d_ms_dig = nullptr;
+  ctx->d_ms_fc = nullptr;
+  ctx->d_ms_rows = ctx->d_ms_yhat = ctx->d_ms_mom = nullptr;
+  ctx->ms_cap = 0;
+  ctx->ms_bias.clear();
+  ctx->ms_set.clear();
+}
+
+void models_release(bann_ctx* ctx) { models_free(ctx); }  // bann_ctx_destroy
+
+static DevState slot_state(const bann_ctx* ctx, int32_t k) {
+  DevState s = ctx->st;
+  s.theta = ctx->d_ms_theta + (int64_t)k * ctx->total_p;
+  s.dig = ctx->d_ms_dig + (int64_t)k * ctx->ms_dig_bytes;
+  s.fc = ctx->d_ms_fc + (int64_t)k * (int64_t)ctx->br.size();
+  s.pred = ctx->d_ms_rows;
+  return s;
+}
+
+static int models_ready(bann_ctx* ctx) {
+  if (!ctx) return BANN_E_ARG;
+  if (!ctx->finalized) return fail(ctx, BANN_E_STATE, "call bann_finalize first");
+  if (ctx->lf_active) return fail(ctx, BANN_E_STATE, "a leapfrog session is active");
+  return BANN_OK;
+}
+
+extern "C" int bann_models_pass_width(void) { return BANN_FE_KM; }
+
+extern "C" int bann_models_capacity(const bann_ctx* ctx) { return ctx ? ctx->ms_cap : 0; }
+
+extern "C" int bann_models_reserve(bann_ctx* ctx, int32_t num_models) {
+  int rc = models_ready(ctx);
+  if (rc) return rc;
+  if (num_models < 0) return fail(ctx, BANN_E_ARG, "negative model count");
+  CK(hipStreamSynchronize(ctx->stream));
+  models_free(ctx);
+  if (num_models == 0) return BANN_OK;
+  const int64_t nb = (int64_t)ctx->br.size(), K = num_models;
+  int64_t dig_bytes = 0;  // the digit image as plan_layout sizes it
+  for (const BranchHost& h : ctx->br)
+    if (h.dev.fused != PATH_GX)
+      dig_bytes = std::max(dig_bytes, h.dev.dig_off + (int64_t)h.dev.nchunks * 1024 * (h.dev.fused == PATH_WX ? 8 : 1));
+  ctx->ms_dig_bytes = (dig_bytes + 15) / 16 * 16;
+  auto alloc_all = [&]() -> hipError_t {
+    hipError_t e;
+    if ((e = dalloc(&ctx->d_ms_theta, K * ctx->total_p)) != hipSuccess) return e;
+    if ((e = dalloc(&ctx->d_ms_dig, K * ctx->ms_dig_bytes)) != hipSuccess) return e;
+    if ((e = dalloc(&ctx->d_ms_fc, K * nb)) != hipSuccess) return e;
+    if ((e = dalloc(&ctx->d_ms_rows, (int64_t)BANN_FE_KM * nb * ctx->n)) != hipSuccess) return e;
+    if ((e = dalloc(&ctx->d_ms_yhat, K * ctx->n)) != hipSuccess) return e;
+    if ((e = dalloc(&ctx->d_ms_mom, 2 * ctx->n)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(ctx->d_ms_theta, 0, (size_t)std::max<int64_t>(K * ctx->total_p, 1) * sizeof(float),
+                            ctx->stream)) != hipSuccess)
+      return e;
+    // the padding rows of a digit image stay zero, as in the live image (alloc_branch_state)
+    if ((e = hipMemsetAsync(ctx->d_ms_dig, 0, (size_t)std::max<int64_t>(K * ctx->ms_dig_bytes, 1), ctx->stream)) !=
+        hipSuccess)
+      return e;
+    if ((e = hipMemsetAsync(ctx->d_ms_fc, 0, (size_t)(K * nb) * sizeof(FusedConst), ctx->stream)) != hipSuccess) return e;
+    return hipStreamSynchronize(ctx->stream);
+  };
+  const hipError_t e = alloc_all();
+  if (e != hipSuccess) {
+    models_free(ctx);
+    return fail(ctx, e == hipErrorOutOfMemory ? BANN_E_OOM : BANN_E_HIP,
+                std::string("bann_models_reserve: ") + hipGetErrorString(e));
+  }
+  ctx->ms_cap = num_models;
+  ctx->ms_bias.assign((size_t)K, 0.f);
+  ctx->ms_set.assign((size_t)(K * nb), 0);
+  return BANN_OK;
+}
+
+extern "C" int bann_models_set_params(bann_ctx* ctx, int32_t k, int32_t b, const float* param_vec) {
+  int rc = models_ready(ctx);
+  if (rc) return rc;
+  if (k < 0 || k >= ctx->ms_cap) return fail(ctx, BANN_E_ARG, "model slot out of range");
+  if (!check_branch(ctx, b) || !param_vec) return fail(ctx, BANN_E_ARG, "bad branch or null params");
+  const BranchHost& h = ctx->br[b];
+  const DevState s = slot_state(ctx, k);
+  CK(hipMemcpyAsync(s.theta + h.dev.p_off, param_vec, h.P * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  int32_t bb = b;
+  CK(hipMemcpyAsync(ctx->d_list_scr, &bb, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  launch_fused_const(s, ctx->d_list_scr, 1, ctx->stream);  // the slot's digits and constants: the live path's bits
+  CK(hipGetLastError());
+  CK(hipStreamSynchronize(ctx->stream));
+  ctx->ms_set[(size_t)k * ctx->br.size() + b] = 1;
+  return BANN_OK;
+}
+
+extern "C" int bann_models_set_bias(bann_ctx* ctx, int32_t k, float bias) {
+  int rc = models_ready(ctx);
+  if (rc) return rc;
+  if (k < 0 || k >= ctx->ms_cap) return fail(ctx, BANN_E_ARG, "model slot out of range");
+  ctx->ms_bias[k] = bias;
+  return BANN_OK;
+}
+
+// the rows of slots k0 .. k0 + nk (nk <= BANN_FE_KM) for the plan's branches into the pass
+// scratch ([model][branch][n]): fx groups through the multi-model forward, every other path
+// per model through its own forward launches on the slot state
+static int models_pass(bann_ctx* ctx, const Plan& p, int32_t k0, int32_t nk, FeModels& mm) {
+  const int64_t nb = (int64_t)ctx->br.size();
+  DevState sj[BANN_FE_KM];
+  mm = FeModels{};
+  mm.nk = nk;
+  for (int j = 0; j < nk; ++j) {
+    sj[j] = slot_state(ctx, k0 + j);
+    sj[j].pred = ctx->d_ms_rows + (int64_t)j * nb * ctx->n;
+    mm.theta[j] = sj[j].theta;
+    mm.dig[j] = sj[j].dig;
+    mm.fc[j] = sj[j].fc;
+    mm.pred[j] = sj[j].pred;
+    mm.bias[j] = ctx->ms_bias[k0 + j];
+  }
+  for (const auto& g : p.groups) {
+    if (g.kind == PATH_FX) {
+      launch_forward_fe(ctx->st, mm, g.d_items, (int32_t)g.items.size(), g.L, g.act, ctx->stream);
+    } else {
+      for (int j = 0; j < nk; ++j) launch_group_grad(ctx, sj[j], g, 1, -1, 0, nullptr, nullptr);
+    }
+  }
+  if (!p.gxg.empty())
+    for (int j = 0; j < nk; ++j) launch_gx_phases(ctx, sj[j], p, true);
+  CK(hipGetLastError());
+  return BANN_OK;
+}
+
+extern "C" int bann_models_predict(bann_ctx* ctx, int32_t k0, int32_t nk, float* y_hat_out, float* mean_out,
+                                   float* var_out) {
+  int rc = models_ready(ctx);
+  if (rc) return rc;
+  if (!y_hat_out) return fail(ctx, BANN_E_ARG, "null output");
+  if (k0 < 0 || nk <= 0 || (int64_t)k0 + nk > ctx->ms_cap) return fail(ctx, BANN_E_ARG, "model slots out of range");
+  const int32_t nb = (int32_t)ctx->br.size();
+  for (int32_t k = k0; k < k0 + nk; ++k)
+    for (int32_t b = 0; b < nb; ++b)
+      if (!ctx->ms_set[(size_t)k * nb + b])
+        return fail(ctx, BANN_E_STATE, "model slot " + std::to_string(k) + ": branch " + std::to_string(b) +
+                                           " has no parameters");
+  std::vector<int32_t> all(nb);
+  for (int32_t b = 0; b < nb; ++b) all[b] = b;
+  Plan p;
+  rc = build_plan(ctx, all.data(), nb, p, false);
+  if (rc) return rc;
+  for (int32_t j0 = 0; j0 < nk; j0 += BANN_FE_KM) {
+    FeModels mm;
+    rc = models_pass(ctx, p, k0 + j0, std::min<int32_t>(BANN_FE_KM, nk - j0), mm);
+    if (rc) return rc;
+    launch_models_sum(mm, nb, ctx->n, ctx->d_ms_yhat + (int64_t)j0 * ctx->n, ctx->stream);
+  }
+  if (mean_out || var_out)
+    launch_models_moments(ctx->d_ms_yhat, nk, ctx->n, mean_out ? ctx->d_ms_mom : nullptr,
+                          var_out ? ctx->d_ms_mom + ctx->n : nullptr, ctx->stream);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(y_hat_out, ctx->d_ms_yhat, (size_t)nk * ctx->n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (mean_out) CK(hipMemcpyAsync(mean_out, ctx->d_ms_mom, ctx->n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (var_out)
+    CK(hipMemcpyAsync(var_out, ctx->d_ms_mom + ctx->n, ctx->n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  return BANN_OK;
+}
+
+extern "C" int bann_models_branch_predictions(bann_ctx* ctx, int32_t k, const int32_t* branches, int32_t nb,
+                                              float* pred_out) {
+  int rc = models_ready(ctx);
+  if (rc) return rc;
+  if (!branches || nb <= 0 || !pred_out) return fail(ctx, BANN_E_ARG, "bad branch list or null output");
+  if (k < 0 || k >= ctx->ms_cap) return fail(ctx, BANN_E_ARG, "model slot out of range");
+  for (int32_t i = 0; i < nb; ++i) {
+    if (!check_branch(ctx, branches[i])) return fail(ctx, BANN_E_ARG, "branch out of range");
+    if (!ctx->ms_set[(size_t)k * ctx->br.size() + branches[i]])
+      return fail(ctx, BANN_E_STATE, "model slot " + std::to_string(k) + ": branch " + std::to_string(branches[i]) +
+                                         " has no parameters");
+  }
+  Plan p;
+  rc = build_plan(ctx, branches, nb, p, false);
+  if (rc) return rc;
+  FeModels mm;
+  rc = models_pass(ctx, p, k, 1, mm);
+  if (rc) return rc;
+  for (int32_t i = 0; i < nb; ++i)
+    CK(hipMemcpyAsync(pred_out + (int64_t)i * ctx->n, mm.pred[0] + (int64_t)branches[i] * ctx->n, ctx->n * sizeof(float),
+                      hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
   return BANN_OK;
 }

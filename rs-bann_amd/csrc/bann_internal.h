@@ -251,6 +251,24 @@ void launch_forward_fi(const DevState& st, const GradItem* items, int32_t nitems
                        int32_t act, int32_t max_seg, int32_t cus, int32_t waves_per_simd, hipStream_t s);
 void launch_pack_fi(const uint8_t* raw, int64_t rowb, const PackJob* jobs, int32_t njobs, const int32_t* idx,
                     int64_t ntile, uint8_t* dst, hipStream_t s);
+// multi-model forward of the fx branches (kernels_fe.hip): the models of one pass over the
+// model slots (bann_models_*), each with its own parameters, W0 digits and fused constants;
+// model j writes the row of branch b at pred[j] + BranchDev::y_off
+#define BANN_FE_KM 4  // models per genotype pass
+struct FeModels {
+  int32_t nk;  // models of this pass, 1 .. BANN_FE_KM
+  const float* theta[BANN_FE_KM];
+  const uint8_t* dig[BANN_FE_KM];
+  const FusedConst* fc[BANN_FE_KM];
+  float* pred[BANN_FE_KM];
+  float bias[BANN_FE_KM];  // output bias (launch_models_sum)
+};
+void launch_forward_fe(const DevState& st, const FeModels& mm, const GradItem* items, int32_t nitems, int32_t L,
+                       int32_t act, hipStream_t s);
+// out[j][i] = (0 + bias_j) + sum over b < nb (branch order) of pred[j][b n + i], in f32 (Net::predict)
+void launch_models_sum(const FeModels& mm, int32_t nb, int64_t n, float* out, hipStream_t s);
+// over nk rows of n: mean and the two-pass sample variance (0 for nk = 1), f64 accumulation; either may be null
+void launch_models_moments(const float* rows, int32_t nk, int64_t n, float* mean, float* var, hipStream_t s);
 void launch_fused_grad_fxl(const DevState& st, const GradItem* items, int32_t nitems, int32_t L, int32_t act,
                            int32_t nw, int32_t cpw, int full, int write_pred, int head, hipStream_t s);
 void launch_step_sizes(const DevState& st, const double* base, const int32_t* branches, int32_t nb, int32_t max_p,

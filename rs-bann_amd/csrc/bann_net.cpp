@@ -1317,8 +1317,19 @@ extern "C" int bann_net_save(const bann_net* t, const char* path) {
   return write_file(const_cast<bann_net*>(t), path);
 }
 
-extern "C" int bann_net_load(bann_net* t, const char* path) {
-  if (!t || !path) return BANN_E_ARG;
+namespace {
+// one parsed Net<B> model file (Net::from_file, net.rs:107-115), checked against the net's branches
+struct ModelFile {
+  bann_precision_hyperparams hp{};
+  std::vector<Branch> br;
+  float ob_e = 0.f, ob_p = 0.f, ob_b = 0.f;
+  uint64_t ns = 0, na = 0, ne = 0, gn = 0;
+  std::vector<float> mse, lpd, l_loc;
+  float l_rss = 0.f, l_out = 0.f, ge = 0.f, go = 0.f, gr = 0.f;
+};
+
+// reads and checks path; touches neither the net's state nor any context
+int parse_model_file(bann_net* t, const char* path, ModelFile& mf) {
   FILE* f = std::fopen(path, "rb");
   if (!f) return fail(t, BANN_E_ARG, std::string("cannot open ") + path);
   std::vector<uint8_t> buf;
@@ -1327,7 +1338,7 @@ extern "C" int bann_net_load(bann_net* t, const char* path) {
   while ((k = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
   std::fclose(f);
   Reader r{buf.data(), buf.size()};
-  bann_precision_hyperparams hp;
+  bann_precision_hyperparams& hp = mf.hp;
   hp.dense_shape = r.f32();
   hp.dense_scale = r.f32();
   hp.summary_shape = r.f32();
@@ -1336,8 +1347,8 @@ extern "C" int bann_net_load(bann_net* t, const char* path) {
   hp.output_scale = r.f32();
   const uint64_t nb = r.u64();
   if (!r.ok || nb != t->br.size() || r.u64() != nb) return fail(t, BANN_E_SHAPE, "branch count differs from the context");
-  std::vector<Branch> br = t->br;
-  for (Branch& B : br) {
+  mf.br = t->br;
+  for (Branch& B : mf.br) {
     const uint64_t P = r.u64(), nw = r.u64(), m = r.u64();
     const auto lw = r.vu64();
     if (!r.ok || P != (uint64_t)B.P || nw != (uint64_t)B.num_weights || m != (uint64_t)B.m || lw.size() != (size_t)B.L)
@@ -1377,36 +1388,102 @@ extern "C" int bann_net_load(bann_net* t, const char* path) {
     B.prec[B.epoff] = ep[0];
     if ((int)r.u32() != B.act) return fail(t, BANN_E_SHAPE, "activation differs from the context");
   }
-  const float ob_e = r.f32(), ob_p = r.f32(), ob_b = r.f32();
-  const uint64_t ns = r.u64(), na = r.u64(), ne = r.u64();
-  const auto mse = r.vf32();
+  mf.ob_e = r.f32(), mf.ob_p = r.f32(), mf.ob_b = r.f32();
+  mf.ns = r.u64(), mf.na = r.u64(), mf.ne = r.u64();
+  mf.mse = r.vf32();
   if (r.u8() != 0) r.vf32();  // mse_test
-  const auto lpd = r.vf32();
-  const float l_rss = r.f32(), l_out = r.f32();
-  const auto l_loc = r.vf32();
-  const float ge = r.f32(), go = r.f32(), gr = r.f32();
-  const uint64_t gn = r.u64();
-  if (!r.ok || r.pos != r.n || l_loc.size() != nb) return fail(t, BANN_E_SHAPE, "truncated or malformed model file");
-  for (size_t b = 0; b < br.size(); ++b) {
-    CKB(bann_branch_set_params(t->ctx, (int32_t)b, br[b].params.data()));
-    CKB(bann_branch_set_precisions(t->ctx, (int32_t)b, br[b].prec.data()));
+  mf.lpd = r.vf32();
+  mf.l_rss = r.f32(), mf.l_out = r.f32();
+  mf.l_loc = r.vf32();
+  mf.ge = r.f32(), mf.go = r.f32(), mf.gr = r.f32();
+  mf.gn = r.u64();
+  if (!r.ok || r.pos != r.n || mf.l_loc.size() != nb) return fail(t, BANN_E_SHAPE, "truncated or malformed model file");
+  return BANN_OK;
+}
+}  // namespace
+
+extern "C" int bann_net_load(bann_net* t, const char* path) {
+  if (!t || !path) return BANN_E_ARG;
+  ModelFile mf;
+  const int prc = parse_model_file(t, path, mf);
+  if (prc < 0) return prc;
+  for (size_t b = 0; b < mf.br.size(); ++b) {
+    CKB(bann_branch_set_params(t->ctx, (int32_t)b, mf.br[b].params.data()));
+    CKB(bann_branch_set_precisions(t->ctx, (int32_t)b, mf.br[b].prec.data()));
   }
-  t->br = std::move(br);
-  t->hp = hp;
-  t->ob_eprec = ob_e;
-  t->ob_prec = ob_p;
-  t->ob_bias = ob_b;
-  t->ns = ns;
-  t->nacc = na;
-  t->nearly = ne;
-  t->mse = mse;
-  t->lpd = lpd;
-  t->lpd_rss = l_rss;
-  t->lpd_outw = l_out;
-  t->lpd_local = l_loc;
-  t->g_eprec = ge;
-  t->g_oprec = go;
-  t->g_reg_sum = gr;
-  t->g_num = gn;
+  t->br = std::move(mf.br);
+  t->hp = mf.hp;
+  t->ob_eprec = mf.ob_e;
+  t->ob_prec = mf.ob_p;
+  t->ob_bias = mf.ob_b;
+  t->ns = mf.ns;
+  t->nacc = mf.na;
+  t->nearly = mf.ne;
+  t->mse = mf.mse;
+  t->lpd = mf.lpd;
+  t->lpd_rss = mf.l_rss;
+  t->lpd_outw = mf.l_out;
+  t->lpd_local = mf.l_loc;
+  t->g_eprec = mf.ge;
+  t->g_oprec = mf.go;
+  t->g_reg_sum = mf.gr;
+  t->g_num = mf.gn;
+  return BANN_OK;
+}
+
+// rs-bann predict (rs-bann.rs:276-312): the model files through the context's model slots, a
+// bounded chunk of slots at a time; every file is parsed and checked before the first row is written
+extern "C" int bann_net_predict_models(bann_net* t, bann_ctx* ctx, const char* const* paths, int32_t num_models,
+                                       float* y_hat_out, float* mean_out, float* var_out) {
+  if (!t || !paths || num_models <= 0 || !y_hat_out) return BANN_E_ARG;
+  bann_ctx* c = ctx ? ctx : t->ctx;
+  const int nb = (int)t->br.size();
+  if (bann_num_branches(c) != nb) return fail(t, BANN_E_SHAPE, "context branch count differs from the net");
+  for (int b = 0; b < nb; ++b) {
+    int32_t m = 0, L = 0, w[BANN_NET_MAXL] = {0};
+    if (bann_branch_info(c, b, &m, &L, w, BANN_NET_MAXL, nullptr, nullptr) != BANN_OK || m != t->br[b].m ||
+        L != t->br[b].L || L > BANN_NET_MAXL || !std::equal(w, w + L, t->br[b].widths.begin()))
+      return fail(t, BANN_E_SHAPE, "context branches differ from the net's");
+  }
+  const int64_t nt = bann_ctx_num_individuals(c);
+  if (nt <= 0) return fail(t, BANN_E_STATE, "context has no cohort");
+  for (int32_t j = 0; j < num_models; ++j) {  // a mismatched file fails the call before any output
+    if (!paths[j]) return fail(t, BANN_E_ARG, "null model path");
+    ModelFile mf;
+    const int prc = parse_model_file(t, paths[j], mf);
+    if (prc < 0) return fail(t, prc, std::string(paths[j]) + ": " + t->err);
+  }
+  const int32_t chunk = std::min<int32_t>(num_models, 4 * std::max(1, bann_models_pass_width()));
+  int rc = bann_models_reserve(c, chunk);
+  if (rc < 0) return fail(t, rc, std::string("predict models: ") + bann_last_error(c));
+  for (int32_t j0 = 0; j0 < num_models && rc >= 0; j0 += chunk) {
+    const int32_t nk = std::min<int32_t>(chunk, num_models - j0);
+    for (int32_t j = 0; j < nk && rc >= 0; ++j) {
+      ModelFile mf;
+      rc = parse_model_file(t, paths[j0 + j], mf);
+      if (rc < 0) break;
+      for (int b = 0; b < nb && rc >= 0; ++b) rc = bann_models_set_params(c, j, b, mf.br[b].params.data());
+      if (rc >= 0) rc = bann_models_set_bias(c, j, mf.ob_b);
+      if (rc < 0) fail(t, rc, std::string("predict models: ") + bann_last_error(c));
+    }
+    if (rc < 0) break;
+    rc = bann_models_predict(c, 0, nk, y_hat_out + (size_t)j0 * nt, nullptr, nullptr);
+    if (rc < 0) fail(t, rc, std::string("predict models: ") + bann_last_error(c));
+  }
+  (void)bann_models_reserve(c, 0);
+  if (rc < 0) return rc;
+  if (mean_out || var_out) {  // over all rows, as bann_models_predict: f64, two passes, rounded once
+    for (int64_t i = 0; i < nt; ++i) {
+      double s = 0.0, q = 0.0;
+      for (int32_t j = 0; j < num_models; ++j) s += (double)y_hat_out[(size_t)j * nt + i];
+      const double mu = s / (double)num_models;
+      for (int32_t j = 0; j < num_models; ++j) {
+        const double d = (double)y_hat_out[(size_t)j * nt + i] - mu;
+        q += d * d;
+      }
+      if (mean_out) mean_out[i] = (float)mu;
+      if (var_out) var_out[i] = num_models > 1 ? (float)(q / (double)(num_models - 1)) : 0.f;
+    }
+  }
   return BANN_OK;
 }

@@ -171,6 +171,18 @@ struct bann_ctx {
   bool u_ev_pending = false;
   // pred_ok[b]: the prediction row of branch b is f_b(theta_b) at the current parameters
   std::vector<char> pred_ok;
+  // model slots (bann_models_*): ms_cap parameter sets beside the live one, allocated by
+  // bann_models_reserve; slot k owns theta / digit image / fused constants number k
+  int32_t ms_cap = 0;
+  int64_t ms_dig_bytes = 0;       // bytes of one digit image
+  float* d_ms_theta = nullptr;    // [ms_cap][total_p]
+  uint8_t* d_ms_dig = nullptr;    // [ms_cap][ms_dig_bytes]
+  FusedConst* d_ms_fc = nullptr;  // [ms_cap][nbranch]
+  float* d_ms_rows = nullptr;     // [BANN_FE_KM][nbranch][n]: the per-branch rows of one pass
+  float* d_ms_yhat = nullptr;     // [ms_cap][n]: the summed rows of a call
+  float* d_ms_mom = nullptr;      // [2][n]: mean, variance
+  std::vector<float> ms_bias;     // [ms_cap]
+  std::vector<char> ms_set;       // [ms_cap][nbranch]: the slot's branch has parameters
   // in-trajectory launch timing (bann_set_launch_timing): HIP events around every
   // gradient and update launch of the leapfrog sessions, resolved at bann_leapfrog_end
   bool tm_on = false;
