@@ -191,6 +191,24 @@ int bann_models_set_bias(bann_ctx* ctx, int32_t k, float bias);
 int bann_models_predict(bann_ctx* ctx, int32_t k0, int32_t nk, float* y_hat_out, float* mean_out, float* var_out);
 /* the per-branch rows f_b of slot k: pred_out is nb x n, row i = branch branches[i] (bann_predict_many) */
 int bann_models_branch_predictions(bann_ctx* ctx, int32_t k, const int32_t* branches, int32_t nb, float* pred_out);
+/* models served by one genotype pass of bann_models_branch_stats (need not equal bann_models_pass_width) */
+int bann_models_stats_pass_width(void);
+/* rs-bann branch-r2 (rs-bann.rs:128-166, Net::branch_r2s net.rs:648-656) and population-effect-sizes
+ * (rs-bann.rs:314-372, net.rs:529-543) over the slots: per model slot k0..k0+nk-1 and listed branch the
+ * rss of f_b against y[n] (rss_out[nk][nb], f64; y and rss_out both NULL: skipped) and the branch's
+ * population effect sizes (pop_out[nk][sum of listed m_b], list order; NULL: skipped).
+ * pop_mean_out / pop_var_out[sum m_b] (nullable): mean and sample variance (nk-1; 0 for nk = 1) over
+ * the nk rows, f64, as bann_models_predict's.  Nothing n-sized leaves the device.  BANN_E_STATE if a
+ * listed branch of a slot of the range was never set; BANN_E_ARG for ranges, duplicate or out-of-range
+ * branches, y without rss_out (and the reverse) or no output at all.  No output is written on error. */
+int bann_models_branch_stats(bann_ctx* ctx, int32_t k0, int32_t nk, const int32_t* branches, int32_t nb,
+                             const float* y, double* rss_out, float* pop_out, float* pop_mean_out,
+                             float* pop_var_out);
+/* the same call, with the HIP-event time (ms) of its statistics-kernel launches alone -- every pass and fx
+ * launch group, without the fold, the other kernel paths and the copies -- in *stats_kernel_ms (0 without
+ * fx branches): the kernel figure of tools/chain_stats_bench.py */
+int bann_models_branch_stats_timed(bann_ctx* ctx, int32_t k0, int32_t nk, const int32_t* branches, int32_t nb,
+                                   const float* y, double* rss_out, float* pop_out, float* stats_kernel_ms);
 /* rss (branch_sampler.rs:905-909) against the branch target */
 int bann_rss(bann_ctx* ctx, int32_t b, double* rss_out);
 /* log_density_gradient (branch_sampler.rs:380-391: backpropagate 813-875 +

@@ -11,6 +11,9 @@
  *   LogPosteriorDensity    src/net/log_posterior_density.rs:18-68
  *   TrainingStats          src/net/train_stats.rs:24-88
  *   GlobalParams           src/net/params.rs:13-63
+ *   branch-r2 / population-effect-sizes over a directory of saved models
+ *                          src/bin/rs-bann.rs:128-166, 314-372 (bann_net_branch_r2s_models,
+ *                          bann_net_population_effect_sizes_models)
  *   Net::to_file/from_file src/net/net.rs:107-115 (bincode 1.3 legacy encoding of
  *                          the Net<B> struct)
  *
@@ -172,6 +175,14 @@ int bann_net_gradient(bann_net* net, bann_ctx* ctx, const float* y, int64_t n, f
 /* Net::branch_r2s (net.rs:648-656, r2 = 1 - rss(x_b, y) / sum y^2,
  * branch_sampler.rs:911-913) for every branch against y[n]; ctx as above */
 int bann_net_branch_r2s(bann_net* net, bann_ctx* ctx, const float* y, int64_t n, float* r2_out);
+/* rs-bann branch-r2 (rs-bann.rs:128-166) over a chain: r2_out[num_models][nb], row j = Net::branch_r2s of
+ * the model file paths[j] against y[n] on the cohort of ctx (NULL: the net's own), r2 formed as in
+ * bann_net_branch_r2s from the f64 rss of bann_models_branch_stats.  File handling as
+ * bann_net_predict_models: every file is parsed first (a mismatching file fails the call before
+ * anything is written), the model slots are reserved in bounded chunks and freed again; the net
+ * and the context's live parameters and targets are unchanged. */
+int bann_net_branch_r2s_models(bann_net* net, bann_ctx* ctx, const char* const* paths, int32_t num_models,
+                               const float* y, int64_t n, float* r2_out);
 /* Net::activations (net.rs:509-518) of branch b: forward_feed's activations of
  * every layer at the net's parameters (bann_forward_feed layout); ctx as above */
 int bann_net_activations(bann_net* net, bann_ctx* ctx, int32_t b, float* act_out);
@@ -179,6 +190,12 @@ int bann_net_activations(bann_net* net, bann_ctx* ctx, int32_t b, float* act_out
  * mean over the individuals of ctx's cohort of effect_sizes (branch_sampler.rs:784-811)
  * at the net's parameters: sum_b m_b floats; ctx as above */
 int bann_net_population_effect_sizes(bann_net* net, bann_ctx* ctx, float* out);
+/* rs-bann population-effect-sizes (rs-bann.rs:314-372) over a chain: out[num_models][sum m_b], row j =
+ * Net::population_effect_sizes of the model file paths[j]; mean_out / var_out[sum m_b] (nullable): mean
+ * and sample variance over the rows, as bann_net_predict_models'.  File handling as
+ * bann_net_branch_r2s_models. */
+int bann_net_population_effect_sizes_models(bann_net* net, bann_ctx* ctx, const char* const* paths,
+                                            int32_t num_models, float* out, float* mean_out, float* var_out);
 int bann_net_summary(const bann_net* net, bann_train_summary* out);
 /* the recorded mse_train / lpd series (TrainingStats::mse_train / lpd);
  * writes min(cap, num_records) entries of each (either may be NULL) */

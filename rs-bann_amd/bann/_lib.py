@@ -168,6 +168,9 @@ SIGNATURES = {
     "bann_models_set_bias": (C.c_int, [_P, _i32, _f32]),
     "bann_models_predict": (C.c_int, [_P, _i32, _i32, _pf32, _pf32, _pf32]),
     "bann_models_branch_predictions": (C.c_int, [_P, _i32, _pi32, _i32, _pf32]),
+    "bann_models_stats_pass_width": (C.c_int, []),
+    "bann_models_branch_stats": (C.c_int, [_P, _i32, _i32, _pi32, _i32, _pf32, _pf64, _pf32, _pf32, _pf32]),
+    "bann_models_branch_stats_timed": (C.c_int, [_P, _i32, _i32, _pi32, _i32, _pf32, _pf64, _pf32, _pf32]),
     "bann_profile_session": (C.c_int, [_P, _i32, _pf32, _pf32]),
     "bann_branch_kernel_path": (C.c_int, [_P, _i32]),
     "bann_set_fused_enabled": (C.c_int, [_P, _i32]),
@@ -188,6 +191,8 @@ SIGNATURES = {
     "bann_net_branch_r2s": (C.c_int, [_P, _P, _pf32, _i64, _pf32]),
     "bann_net_activations": (C.c_int, [_P, _P, _i32, _pf32]),
     "bann_net_population_effect_sizes": (C.c_int, [_P, _P, _pf32]),
+    "bann_net_branch_r2s_models": (C.c_int, [_P, _P, C.POINTER(C.c_char_p), _i32, _pf32, _i64, _pf32]),
+    "bann_net_population_effect_sizes_models": (C.c_int, [_P, _P, C.POINTER(C.c_char_p), _i32, _pf32, _pf32, _pf32]),
     "bann_net_summary": (C.c_int, [_P, C.POINTER(TrainSummary)]),
     "bann_net_records": (C.c_int, [_P, _pf32, _pf32, _i32]),
     "bann_net_residual": (C.c_int, [_P, _pf32]),

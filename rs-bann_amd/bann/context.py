@@ -239,6 +239,38 @@ class BannContext:
                                                              _ptr(out, C.c_float)))
         return out
 
+    def models_stats_pass_width(self) -> int:
+        """models served by one genotype pass of models_branch_stats."""
+        return int(self._lib.bann_models_stats_pass_width())
+
+    def models_branch_stats(self, k0: int = 0, nk: Optional[int] = None, branches=None, y=None, pop: bool = True,
+                            moments: bool = False) -> dict:
+        """per slot k0 .. k0 + nk and listed branch (default: all), without touching the live state:
+        "rss" (nk, nb) f64, the rss of f_b against y (only with y); "pop" (nk, sum m_b), the population
+        effect sizes in list order (only with pop); with moments also "pop_mean" / "pop_var" over the rows."""
+        nk = self.models_capacity() - k0 if nk is None else int(nk)
+        bl = np.ascontiguousarray(range(self.num_branches) if branches is None else branches, dtype=np.int32)
+        summ = sum(self.branch_info(int(b))[0] for b in bl if 0 <= b < self.num_branches)
+        yv = None if y is None else _f32(y)
+        if yv is not None:
+            assert yv.size == self.n, "y length"
+        rss = np.zeros((max(nk, 0), bl.size), np.float64) if yv is not None else None
+        rows = np.zeros((max(nk, 0), summ), np.float32) if pop else None
+        mean = np.zeros(summ, np.float32) if moments else None
+        var = np.zeros(summ, np.float32) if moments else None
+        self._check(self._lib.bann_models_branch_stats(
+            self._h, int(k0), nk, _ptr(bl, C.c_int32), bl.size, _ptr(yv, C.c_float) if yv is not None else None,
+            _ptr(rss, C.c_double) if rss is not None else None, _ptr(rows, C.c_float) if pop else None,
+            _ptr(mean, C.c_float) if moments else None, _ptr(var, C.c_float) if moments else None))
+        out = {}
+        if rss is not None:
+            out["rss"] = rss
+        if pop:
+            out["pop"] = rows
+        if moments:
+            out["pop_mean"], out["pop_var"] = mean, var
+        return out
+
     def rss(self, b: int) -> float:
         r = C.c_double()
         self._check(self._lib.bann_rss(self._h, b, C.byref(r)))

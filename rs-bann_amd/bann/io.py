@@ -7,10 +7,13 @@
   read_phen/write_phen Phenotypes::from_file / to_file (data/phenotypes.rs:28-36)
   list_model_files / write_predictions_csv   the model listing and the CSV records of
                       rs-bann predict (rs-bann.rs:288-311); pure Python
+  write_branch_r2_csv / write_population_effect_sizes_json   the outputs of rs-bann branch-r2
+                      (rs-bann.rs:128-166) and population-effect-sizes (314-372); pure Python
 """
 from __future__ import annotations
 
 import ctypes as C
+import json
 import os
 from typing import List
 
@@ -90,3 +93,25 @@ def write_predictions_csv(file, rows) -> None:
     (rs-bann.rs:308-309).  file: a text file object."""
     for row in np.atleast_2d(np.asarray(rows, dtype=np.float32)):
         file.write(",".join(format_f32(v) for v in row) + "\n")
+
+
+def write_branch_r2_csv(file, rows) -> None:
+    """one record per model: the branch r2 values, comma separated, newline terminated, values as
+    f32::to_string (the reference prints both this and the predictions with e.to_string()).
+    file: a text file object."""
+    write_predictions_csv(file, rows)
+
+
+def write_population_effect_sizes_json(path, values) -> None:
+    """the population effect sizes as one flat JSON array of numbers, each the shortest decimal that
+    parses back to the same f32.  Byte-equality with serde_json's float formatting is NOT claimed
+    (it switches to exponents where this writer keeps positional digits); the parsed values are
+    identical.  JSON has no NaN or infinity: a non-finite value raises ValueError and nothing is written."""
+    v = np.asarray(values, dtype=np.float32).ravel()
+    if not np.all(np.isfinite(v)):
+        raise ValueError("non-finite population effect size: not representable in JSON")
+    # "-0" would parse as the integer 0 and lose its sign: every number carries a fraction part
+    text = "[" + ",".join(t if "." in t else t + ".0" for t in map(format_f32, v)) + "]"
+    json.loads(text)  # well-formed by construction; a cheap guard against a formatting slip
+    with open(path, "w") as f:
+        f.write(text)

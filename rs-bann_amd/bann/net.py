@@ -176,6 +176,25 @@ class Net:
                                                   v.size, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def branch_r2s_models(self, paths, y, ctx=None) -> np.ndarray:
+        """rs-bann branch-r2 (rs-bann.rs:128-166) over a chain: (len(paths), nb), row j = branch_r2s of the
+        model file paths[j], through the context's model slots -- this net and the context's live
+        parameters and targets are unchanged.  A file that does not match the net raises first."""
+        c = ctx if ctx is not None else self._ctx
+        paths = [str(p) for p in paths]
+        arr = (C.c_char_p * max(len(paths), 1))(*[p.encode() for p in paths])
+        v = np.ascontiguousarray(y, dtype=np.float32)
+        out = np.zeros((len(paths), c.num_branches), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.bann_net_branch_r2s_models(self._h, self._ctxh(ctx), arr, len(paths),
+                                                         v.ctypes.data_as(fp), v.size, out.ctypes.data_as(fp)))
+        return out
+
+    def branch_r2s_dir(self, model_dir: str, y, ctx=None) -> np.ndarray:
+        """branch_r2s_models over every regular file of model_dir in sorted order."""
+        from .io import list_model_files
+        return self.branch_r2s_models(list_model_files(model_dir), y, ctx=ctx)
+
     def activations(self, b: int, ctx=None):
         """Net::activations (net.rs:509-518) of branch b: per layer an [n, w_l] array."""
         c = ctx if ctx is not None else self._ctx
@@ -197,6 +216,28 @@ class Net:
         self._check(self._lib.bann_net_population_effect_sizes(self._h, self._ctxh(ctx),
                                                                out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def population_effect_sizes_models(self, paths, ctx=None, moments: bool = False):
+        """rs-bann population-effect-sizes (rs-bann.rs:314-372) over a chain: (len(paths), sum m_b), row j =
+        population_effect_sizes of the model file paths[j], through the context's model slots -- this
+        net and the context's live parameters are unchanged.  moments: also (mean, var) over the rows."""
+        c = ctx if ctx is not None else self._ctx
+        paths = [str(p) for p in paths]
+        arr = (C.c_char_p * max(len(paths), 1))(*[p.encode() for p in paths])
+        summ = sum(c.branch_info(b)[0] for b in range(c.num_branches))
+        out = np.zeros((len(paths), summ), np.float32)
+        mean = np.zeros(summ, np.float32) if moments else None
+        var = np.zeros(summ, np.float32) if moments else None
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.bann_net_population_effect_sizes_models(
+            self._h, self._ctxh(ctx), arr, len(paths), out.ctypes.data_as(fp),
+            mean.ctypes.data_as(fp) if moments else None, var.ctypes.data_as(fp) if moments else None))
+        return (out, mean, var) if moments else out
+
+    def population_effect_sizes_dir(self, model_dir: str, ctx=None, moments: bool = False):
+        """population_effect_sizes_models over every regular file of model_dir in sorted order."""
+        from .io import list_model_files
+        return self.population_effect_sizes_models(list_model_files(model_dir), ctx=ctx, moments=moments)
 
     def summary(self) -> dict:
         s = TrainSummary()

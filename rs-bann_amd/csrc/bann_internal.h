@@ -269,6 +269,37 @@ void launch_forward_fe(const DevState& st, const FeModels& mm, const GradItem* i
 void launch_models_sum(const FeModels& mm, int32_t nb, int64_t n, float* out, hipStream_t s);
 // over nk rows of n: mean and the two-pass sample variance (0 for nk = 1), f64 accumulation; either may be null
 void launch_models_moments(const float* rows, int32_t nk, int64_t n, float* mean, float* var, hipStream_t s);
+// multi-model branch statistics of the fx branches (kernels_fs.hip): per (model, work item) one
+// record of five doubles -- the rss of the branch output against y (0 with y = null) and the
+// column sums s_0 .. s_3 of the effect-size chain's first-layer deltas -- at
+// part + j model_stride + 5 item for model j of the pass; nothing n-sized is written
+#ifndef BANN_FS_KM
+#define BANN_FS_KM 3  // models per genotype pass (register budget: DESIGN.md 4.8)
+#endif
+struct FsModels {
+  int32_t nk;  // models of this pass, 1 .. BANN_FS_KM
+  const float* theta[BANN_FS_KM];
+  const uint8_t* dig[BANN_FS_KM];
+  const FusedConst* fc[BANN_FS_KM];
+};
+void launch_stats_fe(const DevState& st, const FsModels& mm, const GradItem* items, int32_t nitems, int32_t L,
+                     int32_t act, const float* y, double* part, int64_t model_stride, hipStream_t s);
+// one listed fx branch: its records (item_begin .. + item_count in the call's item order) and where
+// its results go (rss column list_ix, pop columns pop_off .. + m)
+struct FsFoldJob {
+  int32_t branch;
+  int32_t list_ix;
+  int32_t item_begin;
+  int32_t item_count;
+  int64_t pop_off;
+};
+// per job and model k < nk (parameters at theta0 + k theta_stride): the records folded in item order,
+// rss[k rss_stride + list_ix] and pop[k pop_stride + pop_off + j] = sum_k W0(j, k) s_k / n; either may be null
+void launch_stats_fold(const DevState& st, const float* theta0, int64_t theta_stride, int32_t nk,
+                       const FsFoldJob* jobs, int32_t njobs, const double* part, int64_t model_stride, double* rss,
+                       int32_t rss_stride, float* pop, int64_t pop_stride, hipStream_t s);
+// *out = sum_i (row[i] - y[i])^2, f64, fixed order
+void launch_row_rss(const float* row, const float* y, int64_t n, double* out, hipStream_t s);
 void launch_fused_grad_fxl(const DevState& st, const GradItem* items, int32_t nitems, int32_t L, int32_t act,
                            int32_t nw, int32_t cpw, int full, int write_pred, int head, hipStream_t s);
 void launch_step_sizes(const DevState& st, const double* base, const int32_t* branches, int32_t nb, int32_t max_p,

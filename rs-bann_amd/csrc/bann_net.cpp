@@ -1431,12 +1431,14 @@ extern "C" int bann_net_load(bann_net* t, const char* path) {
   return BANN_OK;
 }
 
-// rs-bann predict (rs-bann.rs:276-312): the model files through the context's model slots, a
-// bounded chunk of slots at a time; every file is parsed and checked before the first row is written
-extern "C" int bann_net_predict_models(bann_net* t, bann_ctx* ctx, const char* const* paths, int32_t num_models,
-                                       float* y_hat_out, float* mean_out, float* var_out) {
-  if (!t || !paths || num_models <= 0 || !y_hat_out) return BANN_E_ARG;
-  bann_ctx* c = ctx ? ctx : t->ctx;
+// The common part of the chain-level calls (rs-bann predict / branch-r2 / population-effect-sizes walk
+// a directory of saved models): the context is checked against the net, every file is parsed and
+// checked before anything runs (a mismatched file fails the call before any output), then the files
+// go through the context's model slots a bounded chunk at a time -- pass(j0, nk) sees files
+// j0 .. j0 + nk in slots 0 .. nk -- and the bank is freed.  The net and the live parameters are untouched.
+template <typename Pass>
+static int for_model_chunks(bann_net* t, bann_ctx* c, const char* const* paths, int32_t num_models, const char* what,
+                            Pass&& pass) {
   const int nb = (int)t->br.size();
   if (bann_num_branches(c) != nb) return fail(t, BANN_E_SHAPE, "context branch count differs from the net");
   for (int b = 0; b < nb; ++b) {
@@ -1445,8 +1447,7 @@ extern "C" int bann_net_predict_models(bann_net* t, bann_ctx* ctx, const char* c
         L != t->br[b].L || L > BANN_NET_MAXL || !std::equal(w, w + L, t->br[b].widths.begin()))
       return fail(t, BANN_E_SHAPE, "context branches differ from the net's");
   }
-  const int64_t nt = bann_ctx_num_individuals(c);
-  if (nt <= 0) return fail(t, BANN_E_STATE, "context has no cohort");
+  if (bann_ctx_num_individuals(c) <= 0) return fail(t, BANN_E_STATE, "context has no cohort");
   for (int32_t j = 0; j < num_models; ++j) {  // a mismatched file fails the call before any output
     if (!paths[j]) return fail(t, BANN_E_ARG, "null model path");
     ModelFile mf;
@@ -1455,7 +1456,7 @@ extern "C" int bann_net_predict_models(bann_net* t, bann_ctx* ctx, const char* c
   }
   const int32_t chunk = std::min<int32_t>(num_models, 4 * std::max(1, bann_models_pass_width()));
   int rc = bann_models_reserve(c, chunk);
-  if (rc < 0) return fail(t, rc, std::string("predict models: ") + bann_last_error(c));
+  if (rc < 0) return fail(t, rc, std::string(what) + ": " + bann_last_error(c));
   for (int32_t j0 = 0; j0 < num_models && rc >= 0; j0 += chunk) {
     const int32_t nk = std::min<int32_t>(chunk, num_models - j0);
     for (int32_t j = 0; j < nk && rc >= 0; ++j) {
@@ -1464,26 +1465,91 @@ extern "C" int bann_net_predict_models(bann_net* t, bann_ctx* ctx, const char* c
       if (rc < 0) break;
       for (int b = 0; b < nb && rc >= 0; ++b) rc = bann_models_set_params(c, j, b, mf.br[b].params.data());
       if (rc >= 0) rc = bann_models_set_bias(c, j, mf.ob_b);
-      if (rc < 0) fail(t, rc, std::string("predict models: ") + bann_last_error(c));
+      if (rc < 0) fail(t, rc, std::string(what) + ": " + bann_last_error(c));
     }
     if (rc < 0) break;
-    rc = bann_models_predict(c, 0, nk, y_hat_out + (size_t)j0 * nt, nullptr, nullptr);
-    if (rc < 0) fail(t, rc, std::string("predict models: ") + bann_last_error(c));
+    rc = pass(j0, nk);
+    if (rc < 0) fail(t, rc, std::string(what) + ": " + bann_last_error(c));
   }
   (void)bann_models_reserve(c, 0);
-  if (rc < 0) return rc;
-  if (mean_out || var_out) {  // over all rows, as bann_models_predict: f64, two passes, rounded once
-    for (int64_t i = 0; i < nt; ++i) {
-      double s = 0.0, q = 0.0;
-      for (int32_t j = 0; j < num_models; ++j) s += (double)y_hat_out[(size_t)j * nt + i];
-      const double mu = s / (double)num_models;
-      for (int32_t j = 0; j < num_models; ++j) {
-        const double d = (double)y_hat_out[(size_t)j * nt + i] - mu;
-        q += d * d;
-      }
-      if (mean_out) mean_out[i] = (float)mu;
-      if (var_out) var_out[i] = num_models > 1 ? (float)(q / (double)(num_models - 1)) : 0.f;
+  return rc < 0 ? rc : BANN_OK;
+}
+
+// mean and two-pass sample variance over the num_models rows of n, as bann_models_predict: f64, rounded once
+static void rows_moments(const float* rows, int32_t num_models, int64_t n, float* mean_out, float* var_out) {
+  for (int64_t i = 0; i < n; ++i) {
+    double s = 0.0, q = 0.0;
+    for (int32_t j = 0; j < num_models; ++j) s += (double)rows[(size_t)j * n + i];
+    const double mu = s / (double)num_models;
+    for (int32_t j = 0; j < num_models; ++j) {
+      const double d = (double)rows[(size_t)j * n + i] - mu;
+      q += d * d;
     }
+    if (mean_out) mean_out[i] = (float)mu;
+    if (var_out) var_out[i] = num_models > 1 ? (float)(q / (double)(num_models - 1)) : 0.f;
   }
+}
+
+// rs-bann predict (rs-bann.rs:276-312): the model files through the context's model slots, a
+// bounded chunk of slots at a time; every file is parsed and checked before the first row is written
+extern "C" int bann_net_predict_models(bann_net* t, bann_ctx* ctx, const char* const* paths, int32_t num_models,
+                                       float* y_hat_out, float* mean_out, float* var_out) {
+  if (!t || !paths || num_models <= 0 || !y_hat_out) return BANN_E_ARG;
+  bann_ctx* c = ctx ? ctx : t->ctx;
+  const int64_t nt = bann_ctx_num_individuals(c);
+  const int rc = for_model_chunks(t, c, paths, num_models, "predict models", [&](int32_t j0, int32_t nk) {
+    return bann_models_predict(c, 0, nk, y_hat_out + (size_t)j0 * nt, nullptr, nullptr);
+  });
+  if (rc < 0) return rc;
+  if (mean_out || var_out) rows_moments(y_hat_out, num_models, nt, mean_out, var_out);
+  return BANN_OK;
+}
+
+// rs-bann branch-r2 (rs-bann.rs:128-166) over a chain of model files: row j = Net::branch_r2s
+// (net.rs:648-656) of paths[j], r2 formed as in bann_net_branch_r2s from the slots' f64 rss
+extern "C" int bann_net_branch_r2s_models(bann_net* t, bann_ctx* ctx, const char* const* paths, int32_t num_models,
+                                          const float* y, int64_t n, float* r2_out) {
+  if (!t || !paths || num_models <= 0 || !y || !r2_out) return BANN_E_ARG;
+  bann_ctx* c = ctx ? ctx : t->ctx;
+  if (n != bann_ctx_num_individuals(c)) return fail(t, BANN_E_SHAPE, "y length differs from the context's cohort");
+  const int nb = (int)t->br.size();
+  std::vector<int32_t> all(nb);
+  for (int b = 0; b < nb; ++b) all[b] = b;
+  std::vector<double> rss((size_t)num_models * nb);
+  const int rc = for_model_chunks(t, c, paths, num_models, "branch_r2s models", [&](int32_t j0, int32_t nk) {
+    return bann_models_branch_stats(c, 0, nk, all.data(), nb, y, rss.data() + (size_t)j0 * nb, nullptr, nullptr,
+                                    nullptr);
+  });
+  if (rc < 0) return rc;
+  double yy = 0.0;
+  for (int64_t i = 0; i < n; ++i) yy += (double)y[i] * y[i];
+  for (size_t i = 0; i < rss.size(); ++i) r2_out[i] = 1.f - (float)rss[i] / (float)yy;  // r2 (branch_sampler.rs:911-913)
+  return BANN_OK;
+}
+
+// rs-bann population-effect-sizes (rs-bann.rs:314-372) over a chain of model files: row j =
+// Net::population_effect_sizes (net.rs:529-543) of paths[j]
+extern "C" int bann_net_population_effect_sizes_models(bann_net* t, bann_ctx* ctx, const char* const* paths,
+                                                       int32_t num_models, float* out, float* mean_out,
+                                                       float* var_out) {
+  if (!t || !paths || num_models <= 0 || !out) return BANN_E_ARG;
+  bann_ctx* c = ctx ? ctx : t->ctx;
+  const int nb = (int)t->br.size();
+  std::vector<int32_t> all(nb);
+  int64_t summ = 0;
+  for (int b = 0; b < nb; ++b) {
+    all[b] = b;
+    summ += t->br[b].m;
+  }
+  // the rows land in a staging buffer: a failure in a later chunk leaves `out` untouched
+  std::vector<float> rows((size_t)num_models * summ);
+  const int rc = for_model_chunks(t, c, paths, num_models, "population_effect_sizes models",
+                                  [&](int32_t j0, int32_t nk) {
+                                    return bann_models_branch_stats(c, 0, nk, all.data(), nb, nullptr, nullptr,
+                                                                    rows.data() + (size_t)j0 * summ, nullptr, nullptr);
+                                  });
+  if (rc < 0) return rc;
+  std::copy(rows.begin(), rows.end(), out);
+  if (mean_out || var_out) rows_moments(out, num_models, summ, mean_out, var_out);
   return BANN_OK;
 }

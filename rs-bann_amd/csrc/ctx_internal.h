@@ -183,6 +183,14 @@ struct bann_ctx {
   float* d_ms_mom = nullptr;      // [2][n]: mean, variance
   std::vector<float> ms_bias;     // [ms_cap]
   std::vector<char> ms_set;       // [ms_cap][nbranch]: the slot's branch has parameters
+  // bann_models_branch_stats: scratch grown on first use (caps in elements), released with the bank
+  float* d_bs_y = nullptr;         // [n]: the target vector
+  double* d_bs_part = nullptr;     // [models][work items][5]: k_stats_fe's records
+  double* d_bs_rss = nullptr;      // [models][listed branches]
+  float* d_bs_pop = nullptr;       // [models][sum of listed m_b]
+  float* d_bs_mom = nullptr;       // [2][sum of listed m_b]: mean, variance
+  FsFoldJob* d_bs_jobs = nullptr;  // one per listed fx branch
+  int64_t bs_part_cap = 0, bs_rss_cap = 0, bs_pop_cap = 0, bs_mom_cap = 0, bs_jobs_cap = 0;
   // in-trajectory launch timing (bann_set_launch_timing): HIP events around every
   // gradient and update launch of the leapfrog sessions, resolved at bann_leapfrog_end
   bool tm_on = false;

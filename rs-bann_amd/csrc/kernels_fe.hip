@@ -34,39 +34,13 @@
 
 #include "activations.h"
 #include "bann_internal.h"
+#include "fe_util.h"
 #include "kernel_util.h"
 
 #define FE_WAVES 4
 #define FE_SLOT 8192  // one tile image at <= 8 chunks
 #define FE_KM BANN_FE_KM
 
-typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-
-// one chunk: the four cumulative fragments of a quad-byte operand (fx_fwd_chunk)
-__device__ __forceinline__ void fe_chunk(v4i A, v4u X, v4i (&facc)[4]) {
-  facc[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, (v4i)(X & 0x03030303u), facc[0], 0, 0, 0);
-  facc[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, (v4i)(X & 0x0F0F0F0Fu), facc[1], 0, 0, 0);
-  facc[2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, (v4i)(X & 0x3F3F3F3Fu), facc[2], 0, 0, 0);
-  facc[3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, (v4i)X, facc[3], 0, 0, 0);
-}
-__device__ __forceinline__ v4i fe_rowsum64_acc(v4i A, v4i acc) {
-  return __builtin_amdgcn_mfma_i32_16x16x64_i8(A, v4i{0x40404040, 0x40404040, 0x40404040, 0x40404040}, acc, 0, 0, 0);
-}
-__device__ __forceinline__ float fe_comb4(v4i d) {  // sum_d D_d 2^(-7 d)
-  return (float)d[0] + (float)d[1] * 0x1p-7f + (float)d[2] * 0x1p-14f + (float)d[3] * 0x1p-21f;
-}
-__device__ __forceinline__ void fe_swap32(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                                  false, false);
-  a = __builtin_bit_cast(float, (unsigned)r[0]);
-  b = __builtin_bit_cast(float, (unsigned)r[1]);
-}
-__device__ __forceinline__ void fe_swap16(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                                  false, false);
-  a = __builtin_bit_cast(float, (unsigned)r[0]);
-  b = __builtin_bit_cast(float, (unsigned)r[1]);
-}
 // all but the youngest k (0 .. 8) vector-memory operations of this wave are complete
 __device__ __forceinline__ void fe_vm_wait(int k) {
   switch (k) {
