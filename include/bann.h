@@ -391,6 +391,43 @@ int bann_residual_from_target(bann_ctx* ctx, int32_t b, double* sum, double* sum
  * context's own residual */
 int bann_rebuild_targets(bann_ctx* ctx, const int32_t* branches, int32_t nb, const float* residual_device);
 
+/* ---------------- the Gibbs step on the device ----------------
+ * sample_prior_precisions (ridge_ard.rs:271-301, lasso_ard.rs:271-298, ridge_base.rs / lasso_base.rs)
+ * for every listed branch in one launch: given the parameters the branches' local precisions -- every
+ * entry of precision_vec but the output-layer and the error precision -- are independent draws from
+ * the Gamma posteriors of gibbs_steps.rs:25-57, 76-129, per layer l < L-1 with (k_l, s_l) the
+ * summary pair of hyper for l = L-2 and the dense pair below (params.rs:146-163):
+ *   ARD row j of W_l, ridge   shape out/2 + k_l       scale 2 s_l / (2 + s_l sum_k W(j,k)^2)
+ *   ARD row j of W_l, lasso   shape out + k_l         scale s_l / (1 + s_l sum_k |W(j,k)|)
+ *   whole layer, ridge base   shape k_l + in out / 2  scale 2 s_l / (2 + s_l sum W^2)
+ *   whole layer, lasso base   shape k_l + in out      scale s_l / (1 + s_l sum |W|)
+ *   bias of layer l (ridge)   shape k_l + out / 2     scale 2 s_l / (2 + s_l sum b^2)
+ * The sums are f64 sums of the f32 parameters in a fixed order.  hyper: 6 floats as
+ * bann_hmc_step_joint (the output pair is not read).  BANN_E_STATE before bann_finalize and inside
+ * a leapfrog session; BANN_E_ARG for a null or empty list, duplicate or out-of-range branches, a
+ * null hyper and a std-normal branch (it has no precisions, std_normal_branch.rs:119-131).  The
+ * kernels read no genotypes. */
+
+/* the posterior parameters alone: shape_out / scale_out = the listed branches' precision_vecs
+ * concatenated in list order (sum of num_precisions doubles; the output-layer and error entries
+ * are written as 0), out_stat_out[nb] = the output-weight statistic of each listed branch, sum w^2
+ * for ridge and sum |w| for lasso priors (summary_stat_fn, ridge_ard.rs:39-41, lasso_ard.rs:45-47).
+ * Any output may be NULL, not all of them. */
+int bann_gibbs_posterior(bann_ctx* ctx, const int32_t* branches, int32_t nb, const float* hyper, double* shape_out,
+                         double* scale_out, double* out_stat_out);
+/* sample_param_precisions (branch_sampler.rs:173-188) without its one global draw: every local
+ * precision of every listed branch drawn on the device (Marsaglia-Tsang in f64 on Philox counters;
+ * a draw is a pure function of seed, the branch's index in the context and the entry's index in
+ * precision_vec, rounded to f32 once), the output-layer and the error precision set to the two
+ * arguments (BranchCfg::update_global_params, branch_cfg.rs:59-63).  Afterwards every listed branch
+ * is as if the drawn vector had been passed to bann_branch_set_precisions. */
+int bann_gibbs_sample_precisions(bann_ctx* ctx, const int32_t* branches, int32_t nb, const float* hyper,
+                                 float output_precision, float error_precision, uint64_t seed);
+/* BranchParams::param_vec (params.rs:700-715) of every branch, concatenated in branch order (the
+ * sum of num_params floats): one copy and one host wait, where bann_branch_get_params waits once
+ * per branch */
+int bann_get_params_all(bann_ctx* ctx, float* out);
+
 /* ---------------- multi-GPU: branch shards, one process (rank) per GPU ----------------
  * Branches share no weights: a rank owns a contiguous branch
  * range and only its markers' genotypes.  The context's communicator carries

@@ -25,6 +25,11 @@
  * (north_star: "the Gibbs hyperparameter sweep stays on the host").  Same
  * conventions as bann.h: int status codes, host pointers read or written inside
  * the call and never retained.
+ *
+ * bann_net_train_network trains the same Net with the library's network-joint
+ * sampler (bann_network_hmc_step) instead of the per-branch sweep and writes
+ * the same files; there every branch's precision draws are independent given
+ * the parameters and run on the device (bann.h "the Gibbs step on the device").
  */
 #ifndef BANN_NET_H
 #define BANN_NET_H
@@ -95,7 +100,15 @@ typedef struct {
  * P + Q uniforms (step sizes, [param_vec | precision_vec]), P + Q normals
  * (momentum), the acceptance uniform.  Each sweep of bann_net_train starts
  * with the branch shuffle: nb-1 uniforms (Fisher-Yates, i = nb-1 .. 1,
- * j = floor(u (i+1))); bann_net_train_single_branch draws no shuffle. */
+ * j = floor(u (i+1))); bann_net_train_single_branch draws no shuffle.
+ * bann_net_train_network, per sweep: the error precision (1 gamma); unless fixed precisions,
+ * on the host Gibbs path every branch's local precisions in branch order, each in the order
+ * above (per layer l < L-1 the weight precisions, then the bias precision) -- the device path
+ * draws them on the device from one 64-bit seed of the built-in generator instead -- then the
+ * output-layer precision (1 gamma); the momentum of the whole network (P_total normals in branch
+ * and param_vec order, only while a normal hook is installed: else one 64-bit seed for the device
+ * draw); the acceptance uniform (1 uniform); then, with sampled output bias, 1 gamma + 1 normal.
+ * No shuffle. */
 typedef struct {
   void* user;
   double (*uniform)(void* user);
@@ -144,6 +157,41 @@ int bann_net_train(bann_net* net, const float* y, int64_t n, const bann_mcmc_cfg
  * chain iteration, record_perf / model file / trace after every update */
 int bann_net_train_single_branch(bann_net* net, const float* y, int64_t n, const bann_mcmc_cfg* cfg,
                                  const char* outdir);
+/* Training with the network-joint sampler (bann_network_hmc_step, DESIGN.md 7: no reference
+ * counterpart): each chain iteration is one blocked Gibbs sweep over [precisions | all theta]
+ *   1. the error precision from ridge_posterior(k_out, s_out, rss of the device residual, n)
+ *      (sample_error_precision, branch_sampler.rs:190-202);
+ *   2. unless fixed_param_precisions: every branch's local precisions (sample_prior_precisions),
+ *      then the one output-layer precision from posterior(k_out, s_out, sum_b out_stat_b, g_num),
+ *      ridge or lasso by the prior of branch 0 (a Net has one branch type).  By default the local
+ *      draws run on the device (bann_gibbs_posterior for the nb output statistics, the output
+ *      draw on the host, one bann_gibbs_sample_precisions launch); with BANN_NET_GIBBS_HOST in
+ *      flags, or while a gamma hook is installed, on the host copy of theta in branch order with
+ *      one bann_branch_set_precisions per branch.  Either way every branch ends up with the
+ *      global error and output-layer precision (BranchCfg::update_global_params);
+ *   3. one bann_network_hmc_step over every branch at the new error precision (Izmailov or
+ *      uniform step sizes; the context's step rule, bann_set_network_step_rule, as the caller
+ *      left it); num_samples grows by 1 per trajectory;
+ *   4. the output bias as after a branch update (net.rs:319-332, the shape-as-scale quirk of the
+ *      sampled form included; ML form (sum residual + n bias) / n), applied with bann_residual_shift;
+ *   5. the record: the host parameters refreshed by bann_get_params_all, the log posterior
+ *      density recomputed as initialize_stats does (net.rs:158-171: every branch's local terms,
+ *      the output-weight term over the summed statistic, the rss term at the new error
+ *      precision), record_perf, the trace line and after burn-in models/<chain_ix>.bin; at the
+ *      end training_stats.  Start (residual, first record, models/0.bin with burn-in 0) as
+ *      bann_net_train.
+ * The files are those of bann_net_train, so bann_net_predict_models, bann_net_branch_r2s_models and
+ * bann_net_population_effect_sizes_models read them.  BANN_E_ARG for joint_hmc, gradient_descent,
+ * gradient_descent_joint, trajectories, effect_sizes, random or StdScaled step sizes and unknown
+ * flags; BANN_E_STATE for a context whose communicator has more than one rank (the multi-rank
+ * Gibbs step needs the all-reduced output statistic: not built). */
+#define BANN_NET_GIBBS_HOST 1
+int bann_net_train_network(bann_net* net, const float* y, int64_t n, const bann_mcmc_cfg* cfg, int32_t flags,
+                           const char* outdir);
+/* host-clock milliseconds of the last bann_net_train_network call, summed over its sweeps, each
+ * phase ending in a device synchronise: [the Gibbs step (1-2), the trajectories (3), bias and
+ * record (4-5), the whole call] */
+int bann_net_network_timing(const bann_net* net, double out_ms[4]);
 /* Net::perturb (net.rs:187-199, params.rs:219-233, 602-614): add params_by to
  * every weight and bias and / or precisions_by to every precision of every
  * branch (has_* = 0: that part untouched), e.g. to restart a loaded chain */

@@ -160,6 +160,10 @@ SIGNATURES = {
     "bann_branch_get_step_sizes": (C.c_int, [_P, C.c_int32, _P]),
     "bann_predict_many": (C.c_int, [_P, _P, C.c_int32, _P]),
     "bann_synchronize": (C.c_int, [_P]),
+    # the Gibbs step on the device
+    "bann_gibbs_posterior": (C.c_int, [_P, _pi32, _i32, _pf32, _pf64, _pf64, _pf64]),
+    "bann_gibbs_sample_precisions": (C.c_int, [_P, _pi32, _i32, _pf32, _f32, _f32, _u64]),
+    "bann_get_params_all": (C.c_int, [_P, _pf32]),
     # model slots: a chain of saved models from one genotype pass
     "bann_models_reserve": (C.c_int, [_P, _i32]),
     "bann_models_capacity": (C.c_int, [_P]),
@@ -183,6 +187,8 @@ SIGNATURES = {
     "bann_net_set_global": (C.c_int, [_P, _f32, _f32, _f32, _f32]),
     "bann_net_train": (C.c_int, [_P, _pf32, _i64, C.POINTER(McmcCfg), C.c_char_p]),
     "bann_net_train_single_branch": (C.c_int, [_P, _pf32, _i64, C.POINTER(McmcCfg), C.c_char_p]),
+    "bann_net_train_network": (C.c_int, [_P, _pf32, _i64, C.POINTER(McmcCfg), _i32, C.c_char_p]),
+    "bann_net_network_timing": (C.c_int, [_P, _pf64]),
     "bann_net_perturb": (C.c_int, [_P, _i32, _f32, _i32, _f32]),
     "bann_net_predict": (C.c_int, [_P, _P, _pf32]),
     "bann_net_predict_models": (C.c_int, [_P, _P, C.POINTER(C.c_char_p), _i32, _pf32, _pf32, _pf32]),

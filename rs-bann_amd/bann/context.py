@@ -198,6 +198,44 @@ class BannContext:
         self._check(self._lib.bann_predict_many(self._h, _ptr(bl, C.c_int32), bl.size, _ptr(out, C.c_float)))
         return out
 
+    # ------------------------------------------------------ device Gibbs step
+    def _gibbs_args(self, hyper, branches):
+        bl = np.ascontiguousarray(range(self.num_branches) if branches is None else branches, dtype=np.int32)
+        hp = None if hyper is None else _f32(hyper)
+        if hp is not None and hp.size != 6:
+            raise ValueError("hyper needs 6 values")
+        return bl, hp, (None if hp is None else _ptr(hp, C.c_float))
+
+    def gibbs_posterior(self, hyper, branches=None):
+        """posterior Gamma parameters of the local precisions given the current parameters
+        (sample_prior_precisions, ridge_ard.rs:271-301 etc.): (list of per-branch shape vectors,
+        list of per-branch scale vectors, out_stat array), f64, precision_vec order; the
+        output-layer and error entries are 0.  branches None: every branch."""
+        bl, hp, hpp = self._gibbs_args(hyper, branches)
+        sizes = [self.num_precisions(int(b)) for b in bl]
+        sh = np.zeros(max(sum(sizes), 1), np.float64)
+        sc = np.zeros(max(sum(sizes), 1), np.float64)
+        os_ = np.zeros(max(bl.size, 1), np.float64)
+        self._check(self._lib.bann_gibbs_posterior(self._h, _ptr(bl, C.c_int32), bl.size, hpp, _ptr(sh, C.c_double),
+                                                   _ptr(sc, C.c_double), _ptr(os_, C.c_double)))
+        cut = np.cumsum(sizes)[:-1]
+        return np.split(sh[:sum(sizes)], cut), np.split(sc[:sum(sizes)], cut), os_[:bl.size]
+
+    def gibbs_sample_precisions(self, hyper, output_precision: float, error_precision: float, seed: int,
+                                branches=None):
+        """draw every local precision of the listed branches on the device and set the two global
+        ones; afterwards as if the drawn vectors had gone through set_precisions."""
+        bl, hp, hpp = self._gibbs_args(hyper, branches)
+        self._check(self._lib.bann_gibbs_sample_precisions(self._h, _ptr(bl, C.c_int32), bl.size, hpp,
+                                                           float(output_precision), float(error_precision),
+                                                           int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def get_params_all(self) -> np.ndarray:
+        """every branch's param_vec concatenated in branch order: one copy, one wait."""
+        out = np.zeros(sum(self.num_params(b) for b in range(self.num_branches)), np.float32)
+        self._check(self._lib.bann_get_params_all(self._h, _ptr(out, C.c_float)))
+        return out
+
     # ---------------------------------------------------------- model slots
     def models_reserve(self, num_models: int):
         """a bank of num_models parameter sets beside the live one (0 frees it); empties every slot."""

@@ -107,6 +107,26 @@ class Net:
         self._check(self._lib.bann_net_train_single_branch(self._h, v.ctypes.data_as(C.POINTER(C.c_float)), v.size,
                                                            C.byref(cfg.to_c()), outdir.encode() if outdir else None))
 
+    def train_network(self, y, cfg: MCMCConfig = MCMCConfig(), outdir: Optional[str] = None, gibbs: str = "device"):
+        """bann_net_train_network: per chain iteration one blocked Gibbs sweep -- the precisions,
+        then ONE network-joint HMC trajectory over every branch (bann_network_hmc_step), the output
+        bias and the record; the files of ``train``.  gibbs: "device" (the local precisions drawn
+        by the device Gibbs kernels; the default) or "host" (the sequential driver's host draws).
+        While a gamma hook is installed (``set_rng``) the host path runs either way."""
+        if gibbs not in ("device", "host"):
+            raise ValueError('gibbs: "device" or "host"')
+        v = np.ascontiguousarray(y, dtype=np.float32)
+        self._check(self._lib.bann_net_train_network(self._h, v.ctypes.data_as(C.POINTER(C.c_float)), v.size,
+                                                     C.byref(cfg.to_c()), 1 if gibbs == "host" else 0,
+                                                     outdir.encode() if outdir else None))
+
+    def network_timing(self) -> dict:
+        """host-clock milliseconds of the last train_network call: the Gibbs step, the trajectories,
+        bias and record, and the whole call."""
+        out = (C.c_double * 4)()
+        self._check(self._lib.bann_net_network_timing(self._h, out))
+        return {"gibbs_ms": out[0], "trajectory_ms": out[1], "record_ms": out[2], "total_ms": out[3]}
+
     def perturb(self, params_by: Optional[float] = None, precisions_by: Optional[float] = None):
         """Net::perturb (net.rs:187-199): shift every param and / or precision by a constant."""
         self._check(self._lib.bann_net_perturb(self._h, int(params_by is not None), float(params_by or 0.0),

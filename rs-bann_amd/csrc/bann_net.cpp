@@ -8,10 +8,13 @@
 // context's device residual) go through the bann.h entry points; what stays
 // here is what the reference also keeps on the host between branch updates:
 // Gamma/Normal draws from host RNG and scalar log-density terms (net.rs:201-358).
+// bann_net_train_network drives the network-joint sampler instead (one trajectory over every
+// branch per sweep); its local precision draws run on the device (kernels_gibbs.hip).
 #include <sys/stat.h>
 
 #include <algorithm>
 #include <cerrno>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -159,6 +162,8 @@ struct bann_net {
   // test data of record_perf (net.rs:597-610)
   bann_ctx* test_ctx = nullptr;
   std::vector<float> y_test, mse_test;
+  // bann_net_network_timing: the last bann_net_train_network call (Gibbs, trajectories, bias + record, total)
+  double net_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 namespace {
@@ -1104,6 +1109,167 @@ extern "C" int bann_net_train_single_branch(bann_net* t, const float* y, int64_t
   }
   CKB(bann_set_trajectory_recording(t->ctx, 0));
   if (!dir.empty()) return write_training_stats(t, dir);
+  return BANN_OK;
+}
+
+namespace {
+// log_density_joint_wrt_output_weights (ridge_ard.rs:150-169, lasso_ard.rs:153-172) over the
+// network's summed output-weight statistic, at the global output-layer precision
+double ld_out_total(const bann_net* t, bool lasso, double total) {
+  const double shape = t->hp.output_shape, scale = t->hp.output_scale;
+  const double lam = t->g_oprec, num = (double)t->g_num;
+  if (lasso) return -(total + 1.0 / scale) * lam + (shape + num - 1.0) * std::log(lam);
+  return -(0.5 * total + 1.0 / scale) * lam + (shape + (num - 2.0) / 2.0) * std::log(lam);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// one blocked Gibbs sweep of bann_net_train_network (steps 1-5 of include/bann_net.h)
+int network_sweep(bann_net* t, const float* y, const bann_mcmc_cfg* cfg, bool host_gibbs,
+                  const std::vector<int32_t>& all, int64_t p_total, std::vector<float>& theta,
+                  std::vector<float>& mom, std::vector<double>& ostat) {
+  const int nb = (int)t->br.size();
+  const int64_t n = t->n;
+  const double kout = t->hp.output_shape, sout = t->hp.output_scale;
+  const bool lasso = is_lasso(t->br[0].prior);
+  const float hyper[6] = {t->hp.dense_shape, t->hp.dense_scale, t->hp.summary_shape,
+                          t->hp.summary_scale, t->hp.output_shape, t->hp.output_scale};
+  auto t0 = std::chrono::steady_clock::now();
+  // 1. sample_error_precision (branch_sampler.rs:190-202)
+  t->g_eprec = (float)ridge_posterior(t, kout, sout, t->rss_cur, (double)n);
+  // 2. the precisions of every branch given theta
+  bool uploaded = false;
+  if (!cfg->fixed_param_precisions) {
+    double total = 0.0;
+    if (host_gibbs) {
+      for (Branch& B : t->br) {
+        sample_prior_precisions(t, B);
+        total += B.out_stat();
+      }
+    } else {
+      CKB(bann_gibbs_posterior(t->ctx, all.data(), nb, hyper, nullptr, nullptr, ostat.data()));
+      for (int b = 0; b < nb; ++b) total += ostat[b];
+    }
+    t->g_oprec = (float)(lasso ? lasso_posterior(t, kout, sout, total, (double)t->g_num)
+                               : ridge_posterior(t, kout, sout, total, (double)t->g_num));
+    if (!host_gibbs) {
+      CKB(bann_gibbs_sample_precisions(t->ctx, all.data(), nb, hyper, t->g_oprec, t->g_eprec, t->gen()));
+      for (int b = 0; b < nb; ++b) CKB(bann_branch_get_precisions(t->ctx, b, t->br[b].prec.data()));
+      uploaded = true;
+    }
+  }
+  if (!(t->g_eprec >= 0.f) || !(t->g_oprec >= 0.f))
+    return fail(t, BANN_E_STATE, "invalid global parameter in the Gibbs step (params.rs:42-54)");
+  for (int b = 0; b < nb; ++b) {  // BranchCfg::update_global_params (branch_cfg.rs:59-63)
+    cfg_update_global(t, t->br[b]);
+    if (!uploaded) CKB(bann_branch_set_precisions(t->ctx, b, t->br[b].prec.data()));
+  }
+  CKB(bann_synchronize(t->ctx));
+  t->net_ms[0] += ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  // 3. one trajectory over every branch
+  const bool dev_mom = !t->hooks.normal;
+  uint64_t mseed = 0;
+  if (dev_mom) {
+    mseed = t->gen();
+  } else {
+    mom.resize(p_total);
+    for (auto& p : mom) p = (float)draw_normal(t);
+  }
+  const float u = (float)draw_uniform(t);
+  int32_t status = 0;
+  CKB(bann_network_hmc_step(t->ctx, y, t->ob_bias, t->g_eprec, cfg->hmc_integration_length,
+                            cfg->hmc_max_hamiltonian_error, cfg->hmc_step_size_mode, cfg->hmc_step_size_factor,
+                            nullptr, dev_mom ? nullptr : mom.data(), mseed, &u, &status, nullptr, nullptr));
+  ++t->ns;  // TrainingStats::add_hmc_step_result (train_stats.rs:46-53)
+  if (status == BANN_ACCEPTED) ++t->nacc;
+  if (status == BANN_REJECTED_EARLY) ++t->nearly;
+  CKB(bann_synchronize(t->ctx));
+  t->net_ms[1] += ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  // 4. output bias (net.rs:319-332): residual += bias, draw, residual -= bias
+  t->ob_eprec = t->g_eprec;
+  double sr = 0.0;
+  CKB(bann_residual_shift(t->ctx, t->ob_bias, &sr, nullptr));
+  if (cfg->sampled_output_bias) {
+    // sample_prior_precision passes the prior SHAPE as the scale (net.rs:61-66)
+    const double bsq = (double)t->ob_bias * t->ob_bias;
+    t->ob_prec = (float)draw_gamma(t, kout + 0.5, 2.0 * kout / (2.0 + kout * bsq));
+    const double den = (double)n * t->ob_eprec + t->ob_prec;  // sample_bias (47-53)
+    t->ob_bias = (float)(t->ob_eprec / den * sr + std::sqrt(1.0 / den) * draw_normal(t));
+  } else {
+    t->ob_bias = (float)(sr / (double)n);  // set_to_maximum_likelihood (43-45)
+  }
+  CKB(bann_residual_shift(t->ctx, -t->ob_bias, nullptr, &t->rss_cur));
+  // 5. the record: host theta, the LPD as initialize_stats forms it (net.rs:158-171)
+  CKB(bann_get_params_all(t->ctx, theta.data()));
+  int64_t o = 0;
+  double total = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    Branch& B = t->br[b];
+    std::copy(theta.begin() + o, theta.begin() + o + B.P, B.params.begin());
+    o += B.P;
+    total += B.out_stat();
+  }
+  t->g_reg_sum = (float)total;
+  for (int b = 0; b < nb; ++b) {
+    t->br[b].ows_reg_sum = t->g_reg_sum;
+    t->lpd_local[b] = (float)ld_joint_local(t, t->br[b]);
+  }
+  t->lpd_outw = (float)ld_out_total(t, lasso, total);
+  const double le = t->g_eprec;
+  t->lpd_rss = (float)(std::log(le) * (kout + (n - 2.0) / 2.0) - le * (t->rss_cur / 2.0 + 1.0 / sout));
+  t->net_ms[2] += ms_since(t0);
+  return BANN_OK;
+}
+}  // namespace
+
+extern "C" int bann_net_train_network(bann_net* t, const float* y, int64_t n, const bann_mcmc_cfg* cfg, int32_t flags,
+                                      const char* outdir) {
+  if (!t || !y || !cfg) return BANN_E_ARG;
+  if (flags & ~BANN_NET_GIBBS_HOST) return fail(t, BANN_E_ARG, "unknown flags");
+  if (cfg->joint_hmc || cfg->gradient_descent || cfg->gradient_descent_joint || cfg->trajectories || cfg->effect_sizes)
+    return fail(t, BANN_E_ARG,
+                "the network sampler has no joint_hmc, gradient_descent, gradient_descent_joint, trajectories or "
+                "effect_sizes mode");
+  if (cfg->hmc_step_size_mode != BANN_STEP_IZMAILOV && cfg->hmc_step_size_mode != BANN_STEP_UNIFORM)
+    return fail(t, BANN_E_ARG, "network sampler step size mode: Izmailov or uniform");
+  int32_t nranks = 1;
+  CKB(bann_comm_info(t->ctx, nullptr, &nranks, nullptr, nullptr));
+  if (nranks > 1)
+    return fail(t, BANN_E_STATE, "bann_net_train_network runs on one rank (the Gibbs step has no all-reduce)");
+  const auto t_all = std::chrono::steady_clock::now();
+  for (double& v : t->net_ms) v = 0.0;
+  const std::string dir = outdir ? outdir : "";
+  bool trace = false, traj = false;
+  int rc = train_begin(t, y, n, cfg, dir, trace, traj);
+  if (rc) return rc;
+  const int nb = (int)t->br.size();
+  const bool host_gibbs = (flags & BANN_NET_GIBBS_HOST) || t->hooks.gamma;
+  std::vector<int32_t> all(nb);
+  int64_t p_total = 0;
+  for (int b = 0; b < nb; ++b) {
+    all[b] = b;
+    p_total += t->br[b].P;
+  }
+  std::vector<float> theta(p_total), mom;
+  std::vector<double> ostat(nb);
+  for (int chain_ix = 1; chain_ix <= cfg->chain_length; ++chain_ix) {
+    if ((rc = network_sweep(t, y, cfg, host_gibbs, all, p_total, theta, mom, ostat))) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = train_record(t, chain_ix, cfg, dir, trace))) return rc;
+    t->net_ms[2] += ms_since(t0);
+  }
+  if (!dir.empty() && (rc = write_training_stats(t, dir))) return rc;
+  t->net_ms[3] = ms_since(t_all);
+  return BANN_OK;
+}
+
+extern "C" int bann_net_network_timing(const bann_net* t, double out_ms[4]) {
+  if (!t || !out_ms) return BANN_E_ARG;
+  std::copy(t->net_ms, t->net_ms + 4, out_ms);
   return BANN_OK;
 }
 

@@ -191,6 +191,12 @@ struct bann_ctx {
   float* d_bs_mom = nullptr;       // [2][sum of listed m_b]: mean, variance
   FsFoldJob* d_bs_jobs = nullptr;  // one per listed fx branch
   int64_t bs_part_cap = 0, bs_rss_cap = 0, bs_pop_cap = 0, bs_mom_cap = 0, bs_jobs_cap = 0;
+  // the device Gibbs step (kernels_gibbs.hip), allocated at its first call
+  double* d_gb_shape = nullptr;  // [total_q]: posterior Gamma shape of every local precision
+  double* d_gb_scale = nullptr;  // [total_q]: its scale
+  double* d_gb_out = nullptr;    // [nbranch]: the output-weight statistic
+  float* d_gb_prec = nullptr;    // [total_q]: the drawn precision vectors (the host mirrors' source)
+  int32_t* d_gb_list = nullptr;  // [nbranch]: the listed branches
   // in-trajectory launch timing (bann_set_launch_timing): HIP events around every
   // gradient and update launch of the leapfrog sessions, resolved at bann_leapfrog_end
   bool tm_on = false;
