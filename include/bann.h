@@ -113,6 +113,42 @@ int bann_genotypes_download(bann_ctx* ctx, const int32_t* snp_idx, int32_t m, in
  * in bounded blocks */
 int bann_genotypes_load_bed(bann_ctx* ctx, const char* stem);
 
+/* ---------------- LD between markers, from the resident cohort ----------------
+ * Replaces the PLINK --r2 run whose table CorrGraph::from_plink_ld (group/centered.rs:54-89) reads:
+ * the reference's group-by-ld does not compute LD itself.  For markers j < k <= j + window, with the
+ * genotype values g in {0,1,2} exactly as the image stores them (a missing .bed code is 0,
+ * bed_lookup_tables.rs:4; PLINK leaves missing pairs out of its sums, this does not):
+ *   s_j = sum g_ij, q_j = sum g_ij^2, S_jk = sum g_ij g_ik                    exact int32
+ *   cov = n S_jk - s_j s_k, v_j = n q_j - s_j^2                               exact int64
+ *   r2  = ((double)cov * (double)cov) / ((double)v_j * (double)v_k)           f64, in this order
+ * and r2 = 0 if v_j == 0 or v_k == 0 (a zero-variance marker is never an edge).  The band holds
+ * (float)r2; an edge is r2 >= (double)r2_min on the f64 value.  BANN_E_SHAPE for n > 536870911,
+ * BANN_E_ARG for window <= 0 or a window whose S band for 128 markers exceeds the scratch limit
+ * (at the default 128 MiB: more than 262144 after clipping to num_markers - 1).  The markers go in
+ * blocks of rows, each with its own S band, statistics, masks and chrom / bp slices: device
+ * scratch is allocated in the call, below 256 MiB whatever num_markers is, and freed at its end. */
+
+/* r2_out[(j-first)*window + d-1] = r2(j, j+d), d = 1..window, j in [first, first+count);
+ * 0 where j+d >= num_markers.  Needs the cohort image: BANN_E_STATE before any
+ * genotypes are loaded and after bann_finalize(free_raw != 0).  Needs no branches. */
+int bann_genotypes_ld_band(bann_ctx* ctx, int32_t window, int64_t first, int64_t count, float* r2_out);
+/* the graph CorrGraph::from_plink_ld builds from the table (centered.rs:54-89), from the band:
+ * symmetric adjacency of {j,k}: 0 < k-j <= window, r2 >= r2_min, and, when chrom / bp
+ * are given (both or neither, num_markers entries), chrom[j] == chrom[k] and (max_bp <= 0 or
+ * |bp[j]-bp[k]| <= max_bp).  Kept in the context until the next ld_graph call or ctx destroy;
+ * num_edges (nullable) receives the number of undirected edges.  The graph does not depend on how
+ * the device work is cut. */
+int bann_genotypes_ld_graph(bann_ctx* ctx, int32_t window, float r2_min, const int32_t* chrom, const int64_t* bp,
+                            int64_t max_bp, int64_t* num_edges);
+/* CSR of the kept graph: offsets[M+1], neighbours[2*num_edges], each list ascending */
+int bann_genotypes_ld_graph_get(bann_ctx* ctx, int64_t* offsets, int32_t* neighbours);
+/* bytes of the S band of one marker block of the calls above (default and maximum 128 MiB;
+ * bytes <= 0 restores the default): a smaller limit means more, smaller blocks on a device that
+ * is short of memory.  Band and graph do not depend on it. */
+int bann_genotypes_ld_scratch_limit(bann_ctx* ctx, int64_t bytes);
+/* HIP-event milliseconds of the device kernels of the last ld_band / ld_graph call */
+int bann_genotypes_ld_timing(const bann_ctx* ctx, double* kernel_ms);
+
 /* ---------------- files on either side of the path (host only, no device) ---------------- */
 /* BedDims (io/dims.rs:15-34): stem.dims "n M", else the .fam / .bim line counts */
 int bann_bed_dims(const char* stem, int64_t* n_out, int64_t* num_markers_out);
@@ -127,6 +163,38 @@ int bann_grouping_uniform(int32_t num_groups, int32_t group_size, int64_t* offse
  * (u64 length + values, little endian).  bann_phen_read with y_out NULL gives n. */
 int bann_phen_read(const char* path, int64_t* n_out, float* y_out);
 int bann_phen_write(const char* path, const float* y, int64_t n);
+/* message of the last failure of a host-only file function below (per thread; "" if none) */
+const char* bann_io_last_error(void);
+/* .bim columns 1 and 4 (whitespace separated, as SNPId2Ix::from_bim splits, centered.rs:15-42):
+ * chrom_out[j] = index of the chromosome string by first appearance, bp_out[j]; outputs nullable
+ * (sizes only).  BANN_E_ARG: no such file; BANN_E_SHAPE: a line with fewer than 4 columns or a
+ * position that is no integer. */
+int bann_bim_read(const char* path, int64_t* num_markers, int32_t* chrom_out, int64_t* bp_out);
+/* CorrGraph::from_plink_ld (centered.rs:54-89): the first line of the PLINK --r2 table is a header,
+ * fields 3 and 6 of every other line are SNP ids looked up in column 2 of the .bim (a repeated id
+ * means its last line, as the reference's map insert); the R2 column is ignored, every listed pair
+ * is an edge, both directions are stored, duplicates collapse, markers without a line are isolated
+ * nodes.  CSR: offsets[M+1], neighbours[2*num_edges] ascending; call with offsets/neighbours NULL
+ * for the sizes.  An id absent from the .bim is BANN_E_ARG with the id in bann_io_last_error (the
+ * reference panics); a line with fewer than 6 fields is BANN_E_SHAPE (blank lines are skipped).
+ * Deviation: a pair of a marker with itself is dropped (the reference would keep the self loop). */
+int bann_ld_graph_read_plink(const char* ld_path, const char* bim_path, int64_t* num_markers, int64_t* num_edges,
+                             int64_t* offsets, int32_t* neighbours);
+/* CorrGraph::centered_grouping (centered.rs:91-133), as it is: the nodes run by (degree descending,
+ * index ascending); a node that is in no group yet founds the next group, its neighbours plus
+ * itself, iff its degree > min_group_size (strictly); otherwise it joins the first existing group
+ * whose GROUP index (not a marker index) equals node - d or node + d, d = 1..99, node - d tried
+ * first and a negative one counted as absent (the release build's wrapping subtraction); a node that
+ * finds none is in no group and is counted in num_ungrouped (nullable).  Markers may belong to
+ * several groups.  Members are written ascending (the reference's order is a hash-set order).
+ * CSR: g_offsets[G+1], g_markers[num_entries]; call with both NULL for the sizes. */
+int bann_grouping_centered(int64_t num_markers, const int64_t* offsets, const int32_t* neighbours,
+                           int32_t min_group_size, int32_t* num_groups, int64_t* num_entries, int64_t* g_offsets,
+                           int32_t* g_markers, int64_t* num_ungrouped);
+/* MarkerGrouping::to_file (grouping.rs:16-31): "{marker}\t{group}\n" per member, group by group,
+ * which bann_grouping_read reads back.  The reference names the file <outdir>/<bim stem>.groups;
+ * here the caller gives the whole path. */
+int bann_grouping_write(const char* path, int32_t num_groups, const int64_t* offsets, const int32_t* markers);
 
 /* ---------------- branches: replaces BranchCfg -> B::from_cfg ----------------
  * branch_struct.rs:12-29 (from_cfg), branch_cfg.rs:185-193 (BranchCfg). */

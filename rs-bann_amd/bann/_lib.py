@@ -94,6 +94,19 @@ SIGNATURES = {
     "bann_phen_read": (C.c_int, [C.c_char_p, C.POINTER(_i64), _pf32]),
     "bann_phen_write": (C.c_int, [C.c_char_p, _pf32, _i64]),
     "bann_genotypes_set_stats": (C.c_int, [_P, _pf32, _pf32]),
+    # LD between markers from the resident cohort; the host side of group-by-ld
+    "bann_genotypes_ld_band": (C.c_int, [_P, _i32, _i64, _i64, _pf32]),
+    "bann_genotypes_ld_graph": (C.c_int, [_P, _i32, _f32, _pi32, C.POINTER(_i64), _i64, C.POINTER(_i64)]),
+    "bann_genotypes_ld_graph_get": (C.c_int, [_P, C.POINTER(_i64), _pi32]),
+    "bann_genotypes_ld_timing": (C.c_int, [_P, _pf64]),
+    "bann_genotypes_ld_scratch_limit": (C.c_int, [_P, _i64]),
+    "bann_io_last_error": (C.c_char_p, []),
+    "bann_bim_read": (C.c_int, [C.c_char_p, C.POINTER(_i64), _pi32, C.POINTER(_i64)]),
+    "bann_ld_graph_read_plink": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_i64), C.POINTER(_i64),
+                                           C.POINTER(_i64), _pi32]),
+    "bann_grouping_centered": (C.c_int, [_i64, C.POINTER(_i64), _pi32, _i32, _pi32, C.POINTER(_i64),
+                                         C.POINTER(_i64), _pi32, C.POINTER(_i64)]),
+    "bann_grouping_write": (C.c_int, [C.c_char_p, _i32, C.POINTER(_i64), _pi32]),
     "bann_genotypes_download": (C.c_int, [_P, _pi32, _i32, _pi8]),
     "bann_branch_add": (C.c_int, [_P, _pi32, _i32, _pi32, _i32, _i32, _i32]),
     "bann_finalize": (C.c_int, [_P, _i32]),

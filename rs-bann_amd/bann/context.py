@@ -107,6 +107,48 @@ class BannContext:
         self._check(self._lib.bann_genotypes_download(self._h, _ptr(idx, C.c_int32), idx.size, _ptr(out, C.c_int8)))
         return out
 
+    # ------------------------------------------------------------------- LD
+    def ld_band(self, window: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """(count, window) f32: row j - first, column d - 1 = r2 of markers j and j + d of the resident
+        cohort (0 where j + d >= num_markers); exact integer sums, one f64 division (include/bann.h)."""
+        if count is None:
+            count = self.num_markers - first
+        out = np.zeros((max(int(count), 0), max(int(window), 0)), np.float32)
+        self._check(self._lib.bann_genotypes_ld_band(self._h, int(window), int(first), int(count),
+                                                     _ptr(out, C.c_float)))
+        return out
+
+    def ld_graph(self, window: int, r2_min: float = 0.2, chrom=None, bp=None, max_bp: int = 0):
+        """(offsets, neighbours): symmetric CSR of the pairs 0 < k - j <= window with r2 >= r2_min, and,
+        with chrom / bp given, on one chromosome and (max_bp <= 0 or) at most max_bp apart."""
+        if (chrom is None) != (bp is None):
+            raise ValueError("chrom and bp are given together or not at all")
+        pc = pb = None
+        if chrom is not None:
+            ca = np.ascontiguousarray(chrom, dtype=np.int32)
+            ba = np.ascontiguousarray(bp, dtype=np.int64)
+            if ca.size != self.num_markers or ba.size != self.num_markers:
+                raise ValueError("chrom and bp need one entry per marker")
+            pc, pb = _ptr(ca, C.c_int32), _ptr(ba, C.c_int64)
+        ne = C.c_int64()
+        self._check(self._lib.bann_genotypes_ld_graph(self._h, int(window), float(r2_min), pc, pb, int(max_bp),
+                                                      C.byref(ne)))
+        off = np.zeros(self.num_markers + 1, np.int64)
+        nb = np.zeros(max(2 * ne.value, 1), np.int32)
+        self._check(self._lib.bann_genotypes_ld_graph_get(self._h, _ptr(off, C.c_int64), _ptr(nb, C.c_int32)))
+        return off, nb[:2 * ne.value]
+
+    def ld_scratch_limit(self, nbytes: int = 0):
+        """bytes of the S band of one marker block of ld_band / ld_graph (0: the default, 128 MiB, also the
+        maximum); the results do not depend on it."""
+        self._check(self._lib.bann_genotypes_ld_scratch_limit(self._h, int(nbytes)))
+
+    def ld_timing(self) -> float:
+        """HIP-event milliseconds of the device kernels of the last ld_band / ld_graph call."""
+        ms = C.c_double()
+        self._check(self._lib.bann_genotypes_ld_timing(self._h, C.byref(ms)))
+        return ms.value
+
     # -------------------------------------------------------------- branches
     def add_branch(self, snp_idx: Sequence[int], layer_widths: Sequence[int], activation: str = "tanh",
                    prior: str = "ridge_ard") -> int:

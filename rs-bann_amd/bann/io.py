@@ -5,6 +5,11 @@
   read_grouping       ExternalGrouping::from_file (group/external.rs:15-60)
   uniform_grouping    UniformGrouping::new (group/uniform.rs:11-23)
   read_phen/write_phen Phenotypes::from_file / to_file (data/phenotypes.rs:28-36)
+  read_bim            .bim chromosome index and position per marker
+  read_plink_ld_graph CorrGraph::from_plink_ld (group/centered.rs:54-89)
+  centered_grouping   CorrGraph::centered_grouping (group/centered.rs:91-133)
+  write_grouping      MarkerGrouping::to_file (group/grouping.rs:16-31)
+  group_by_ld         rs-bann group-by-ld with the LD taken from the context's cohort on the device
   list_model_files / write_predictions_csv   the model listing and the CSV records of
                       rs-bann predict (rs-bann.rs:288-311); pure Python
   write_branch_r2_csv / write_population_effect_sizes_json   the outputs of rs-bann branch-r2
@@ -24,7 +29,8 @@ from ._lib import BannError, load_library
 
 def _chk(rc, what):
     if rc != 0:
-        raise BannError(rc, what)
+        detail = load_library().bann_io_last_error().decode()
+        raise BannError(rc, f"{what}: {detail}" if detail else what)
 
 
 def bed_dims(stem: str):
@@ -52,6 +58,80 @@ def uniform_grouping(num_groups: int, group_size: int) -> List[np.ndarray]:
     _chk(load_library().bann_grouping_uniform(num_groups, group_size, off.ctypes.data_as(C.POINTER(C.c_int64)),
                                               mk.ctypes.data_as(C.POINTER(C.c_int32))), "bann_grouping_uniform")
     return [mk[off[g]:off[g + 1]].copy() for g in range(num_groups)]
+
+
+def read_bim(path: str):
+    """(chrom, bp) of a .bim: int32 chromosome index by first appearance, int64 position."""
+    lib = load_library()
+    m = C.c_int64()
+    _chk(lib.bann_bim_read(path.encode(), C.byref(m), None, None), f"bann_bim_read({path})")
+    chrom = np.zeros(m.value, np.int32)
+    bp = np.zeros(m.value, np.int64)
+    _chk(lib.bann_bim_read(path.encode(), C.byref(m), chrom.ctypes.data_as(C.POINTER(C.c_int32)),
+                           bp.ctypes.data_as(C.POINTER(C.c_int64))), f"bann_bim_read({path})")
+    return chrom, bp
+
+
+def read_plink_ld_graph(ld_path: str, bim_path: str):
+    """(offsets, neighbours): the symmetric CSR graph of a PLINK --r2 table over the .bim's markers."""
+    lib = load_library()
+    m, e = C.c_int64(), C.c_int64()
+    what = f"bann_ld_graph_read_plink({ld_path}, {bim_path})"
+    _chk(lib.bann_ld_graph_read_plink(ld_path.encode(), bim_path.encode(), C.byref(m), C.byref(e), None, None), what)
+    off = np.zeros(m.value + 1, np.int64)
+    nb = np.zeros(max(2 * e.value, 1), np.int32)
+    _chk(lib.bann_ld_graph_read_plink(ld_path.encode(), bim_path.encode(), C.byref(m), C.byref(e),
+                                      off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      nb.ctypes.data_as(C.POINTER(C.c_int32))), what)
+    return off, nb[:2 * e.value]
+
+
+def _csr(groups):
+    off = np.zeros(len(groups) + 1, np.int64)
+    off[1:] = np.cumsum([len(g) for g in groups])
+    mk = np.zeros(max(int(off[-1]), 1), np.int32)
+    for g, members in enumerate(groups):
+        mk[off[g]:off[g + 1]] = members
+    return off, mk
+
+
+def centered_grouping(offsets, neighbours, min_group_size: int = 1):
+    """(groups, num_ungrouped): the centered grouping of a CSR graph, one ascending int32 array per
+    group, and the number of markers that ended in no group."""
+    lib = load_library()
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    nb = np.ascontiguousarray(neighbours, dtype=np.int32)
+    if nb.size == 0:
+        nb = np.zeros(1, np.int32)
+    M = off.size - 1
+    G, E, U = C.c_int32(), C.c_int64(), C.c_int64()
+    p_off, p_nb = off.ctypes.data_as(C.POINTER(C.c_int64)), nb.ctypes.data_as(C.POINTER(C.c_int32))
+    _chk(lib.bann_grouping_centered(M, p_off, p_nb, int(min_group_size), C.byref(G), C.byref(E), None, None,
+                                    C.byref(U)), "bann_grouping_centered")
+    g_off = np.zeros(G.value + 1, np.int64)
+    g_mk = np.zeros(max(E.value, 1), np.int32)
+    _chk(lib.bann_grouping_centered(M, p_off, p_nb, int(min_group_size), C.byref(G), C.byref(E),
+                                    g_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                    g_mk.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(U)), "bann_grouping_centered")
+    return [g_mk[g_off[g]:g_off[g + 1]].copy() for g in range(G.value)], U.value
+
+
+def write_grouping(path: str, groups) -> None:
+    """one "marker<TAB>group" line per member, group by group (read_grouping reads it back)."""
+    off, mk = _csr([np.asarray(g, dtype=np.int32) for g in groups])
+    _chk(load_library().bann_grouping_write(path.encode(), len(groups), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            mk.ctypes.data_as(C.POINTER(C.c_int32))), f"bann_grouping_write({path})")
+
+
+def group_by_ld(ctx, window: int, r2_min: float, min_group_size: int, bim: str = None, max_bp: int = 0):
+    """rs-bann group-by-ld on the context's resident cohort: the LD graph from the device (r2 >= r2_min
+    within window markers; with a .bim also one chromosome and, for max_bp > 0, at most max_bp apart),
+    then the centered grouping.  Returns (groups, num_ungrouped)."""
+    chrom = bp = None
+    if bim is not None:
+        chrom, bp = read_bim(bim)
+    off, nb = ctx.ld_graph(window, r2_min, chrom, bp, max_bp)
+    return centered_grouping(off, nb, min_group_size)
 
 
 def read_phen(path: str) -> np.ndarray:

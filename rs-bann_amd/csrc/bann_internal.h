@@ -315,3 +315,16 @@ void launch_effect_sizes(const DevState& st, int b, const BranchDev& bd, const f
                          float* ea, float* eb, float* full, double* s, float* pop, hipStream_t strm);
 void launch_residual_delta(const DevState& st, const int32_t* branches, int32_t nb, float* scratch, float* out,
                            hipStream_t s);
+// the LD band (kernels_ld.hip): exact integer s_j, q_j of markers j0 .. j0 + m; the S band of rows
+// row0 .. row0 + rows (zeroed by the caller; K split over about ksplit_target workgroups, int32 atomics);
+// S -> the f32 r2 band in place; S -> the thresholded forward bit mask per marker (words per row);
+// st, qt (and chrom, bp) hold the markers from stat0 on
+void launch_ld_stats(const uint8_t* raw, int64_t rowb, int64_t j0, int64_t m, int32_t* s_out, int32_t* q_out,
+                     hipStream_t s);
+void launch_ld_band(const uint8_t* raw, int64_t rowb, int64_t M, int64_t row0, int32_t rows, int32_t window,
+                    int32_t ksplit_target, int32_t* S, hipStream_t s);
+void launch_ld_r2(int32_t* S, int32_t rows, int32_t window, int64_t row0, int64_t M, int64_t n, int64_t stat0,
+                  const int32_t* st, const int32_t* qt, hipStream_t s);
+void launch_ld_mask(const int32_t* S, int32_t rows, int32_t window, int32_t words, int64_t row0, int64_t M, int64_t n,
+                    int64_t stat0, const int32_t* st, const int32_t* qt, double r2_min, const int32_t* chrom,
+                    const int64_t* bp, int64_t max_bp, uint32_t* mask, hipStream_t s);

@@ -197,6 +197,12 @@ struct bann_ctx {
   double* d_gb_out = nullptr;    // [nbranch]: the output-weight statistic
   float* d_gb_prec = nullptr;    // [total_q]: the drawn precision vectors (the host mirrors' source)
   int32_t* d_gb_list = nullptr;  // [nbranch]: the listed branches
+  // the LD graph of the last bann_genotypes_ld_graph call (bann_ld.hip): symmetric CSR, kept on the host
+  std::vector<int64_t> ld_off;
+  std::vector<int32_t> ld_nb;
+  bool ld_have = false;
+  int64_t ld_scratch = int64_t(128) << 20;  // bytes of the S band of one marker block (bann_genotypes_ld_scratch_limit)
+  double ld_ms = 0.0;  // HIP-event time of the device kernels of the last ld_band / ld_graph call
   // in-trajectory launch timing (bann_set_launch_timing): HIP events around every
   // gradient and update launch of the leapfrog sessions, resolved at bann_leapfrog_end
   bool tm_on = false;
