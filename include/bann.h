@@ -163,6 +163,9 @@ int bann_grouping_uniform(int32_t num_groups, int32_t group_size, int64_t* offse
  * (u64 length + values, little endian).  bann_phen_read with y_out NULL gives n. */
 int bann_phen_read(const char* path, int64_t* n_out, float* y_out);
 int bann_phen_write(const char* path, const float* y, int64_t n);
+/* PhenStats::to_file (data/phen_stats.rs:6-24): pretty JSON with the keys mean, variance, env_variance,
+ * each the shortest decimal that reads back to the same f32 (a non-finite value: null) */
+int bann_phen_stats_write(const char* path, float mean, float variance, float env_variance);
 /* message of the last failure of a host-only file function below (per thread; "" if none) */
 const char* bann_io_last_error(void);
 /* .bim columns 1 and 4 (whitespace separated, as SNPId2Ix::from_bim splits, centered.rs:15-42):
@@ -495,6 +498,58 @@ int bann_gibbs_sample_precisions(bann_ctx* ctx, const int32_t* branches, int32_t
  * sum of num_params floats): one copy and one host wait, where bann_branch_get_params waits once
  * per branch */
 int bann_get_params_all(bann_ctx* ctx, float* out);
+
+/* ---------------- starting a model: replaces BlockNetCfg::add_branch / BranchCfgBuilder ----------------
+ * The width rules (architectures.rs:93-122) on the host and the construction of the initial
+ * BranchCfgs (branch_cfg_builder.rs:155-398) on the device. */
+
+/* width rules of one branch (host only): layer_widths_out[depth + 2] = depth hidden widths, the
+ * summary width, 1 -- the array bann_branch_add takes.
+ *   hidden_rule  0: Fixed(hidden_fixed); 1: FractionOfInput(hidden_fraction) =
+ *                max(1, (size_t)((float)m * f)), the f32 product truncated toward zero
+ *   summary_rule 0: Fixed(summary_fixed); 1: LikeHiddenLayerWidth; 2: FractionOfHiddenLayerWidth =
+ *                max(1, (size_t)((float)hidden * f))
+ * depth >= 0; with depth 0 the hidden width is still formed and the summary width derives from it
+ * (add_branch pushes it whatever the depth).  BANN_E_ARG: m < 1, depth < 0 or depth + 2 > 8, an
+ * unknown rule, a fixed width < 1 (Fixed(0) summary: the reference asserts), a fraction that is
+ * negative or no number.  Returns the number of layers depth + 2. */
+int bann_arch_layer_widths(int32_t m, int32_t depth, int32_t hidden_rule, int32_t hidden_fixed, float hidden_fraction,
+                           int32_t summary_rule, int32_t summary_fixed, float summary_fraction,
+                           int32_t* layer_widths_out);
+
+typedef struct {
+  int32_t mode;                 /* 0: weights ~ N(0, 1/m_b), biases 0 (default_param_init, 180-186)
+                                   1: weights and biases ~ N(0, variance) (188-199)
+                                   2: layer l weights ~ N(0, 1/(shape*scale)), biases of layers < L-1 likewise (201-233,
+                                      precisions at the Gamma mean; with_sampled_precisions is not reachable from the CLI) */
+  float variance, gamma_shape, gamma_scale;
+  int32_t num_effective;        /* < 0: unset; takes precedence over proportion (155-168) */
+  float proportion_effective;   /* < 0 or >= 1: every marker kept */
+  int32_t has_fixed_precision;  float fixed_precision;   /* base priors only; ARD: BANN_E_ARG (331) */
+} bann_init_cfg;
+/* BranchCfgBuilder::build / build_base / build_ard for every listed branch, on the device:
+ *  1. theta in param_vec order: entry p is sd * z_p, z_p a standard normal of (seed, the branch's index
+ *     in the context, p) through the inverse distribution function -- a pure function of those three,
+ *     whatever else is listed (the reference draws from an entropy-seeded ChaCha stream: no parity).
+ *  2. the effective markers: a removed marker j has W0(j, k) = 0 for every k (params.rs:580-586).
+ *     num_effective = e keeps exactly e: marker j is kept iff fewer than e markers of the branch come
+ *     before it in the order of (key_j, j), key_j one 32-bit Philox word per marker; e > m_b is
+ *     BANN_E_ARG.  Otherwise proportion_effective = p in [0, 1) keeps j iff u01(key_j) < p.
+ *  3. the precisions in precision_vec order, each the f32 rounding of an f64 quotient over an f64 sum of
+ *     f32 squares in a fixed order: ARD priors (ridge and lasso alike) row j of layer l < L-1
+ *     out_l / sum_k W_l(j,k)^2 and 1 for the output layer (308-328; bann_net_init writes the joint one);
+ *     base and std-normal priors in out / sum W^2 per layer (237-251); the bias of layer l < L-1
+ *     out_l / sum b^2 (264-274); the error precision 2.  With a fixed precision every entry is it.
+ *     A ZERO SUM GIVES +inf, as the reference's f32 division does: every bias precision in mode 0 and
+ *     the ARD row of every removed marker.  Such a branch cannot be evaluated as it is (inf * 0 in the
+ *     prior term); the first Gibbs step of bann_net_train / bann_net_train_network redraws these
+ *     entries before any density reads them, as the reference's does.
+ *  4. afterwards every listed branch is as if the vectors had gone through bann_branch_set_params and
+ *     bann_branch_set_precisions.
+ * BANN_E_STATE before bann_finalize and inside a leapfrog session; BANN_E_ARG for a null, empty,
+ * duplicate or out-of-range list, an unknown mode, mode 1 with variance <= 0, mode 2 with
+ * shape * scale <= 0, a fixed precision <= 0 or with an ARD branch listed.  Nothing is written on error. */
+int bann_init_branches(bann_ctx* ctx, const int32_t* branches, int32_t nb, const bann_init_cfg* cfg, uint64_t seed);
 
 /* ---------------- multi-GPU: branch shards, one process (rank) per GPU ----------------
  * Branches share no weights: a rank owns a contiguous branch

@@ -133,7 +133,8 @@ typedef struct {
  * output-layer precision = branch 0's current output precision, the output
  * weight summary statistic summed over branches (sum of squares for ridge
  * priors, sum of abs for lasso), OutputBias {2, 1, 0}.  The context's branch
- * params / precisions are the initial BranchCfgs.  std-normal branches are
+ * params / precisions are the initial BranchCfgs (bann_net_init replaces them
+ * with build_net's own construction).  std-normal branches are
  * rejected with BANN_E_ARG: the reference panics in Net::train for them
  * (log_posterior_density.rs:55 -> std_normal_branch.rs:129 unimplemented!). */
 int bann_net_create(bann_ctx* ctx, const bann_precision_hyperparams* hp, uint64_t seed, bann_net** out);
@@ -244,6 +245,30 @@ int bann_net_population_effect_sizes(bann_net* net, bann_ctx* ctx, float* out);
  * bann_net_branch_r2s_models. */
 int bann_net_population_effect_sizes_models(bann_net* net, bann_ctx* ctx, const char* const* paths,
                                             int32_t num_models, float* out, float* mean_out, float* var_out);
+/* BlockNetCfg::build_net (architectures.rs:187-237), the construction behind rs-bann train-new and
+ * simulate-y, over the net's context: bann_init_branches over every branch (bann.h: the draws, the
+ * effective markers, the maximum-likelihood precisions, +inf where a sum is zero), then the joint
+ * output-layer precision nb / sum_b sum w_out,b^2 (175-185; f64 on the device from the per-branch
+ * sums, rounded once; the fixed precision when there is one) in every branch's output-layer entry.
+ * The net's BranchCfgs are refreshed from the device and the globals become build_net's (216-236):
+ * error precision 2, output_layer_precision 0.05 or the fixed precision, OutputBias {2, 1, 0},
+ * reg_sum = sum_b summary_stat_fn of the drawn output weights (squares for ridge, absolute values
+ * for lasso), num_params = the sum of the summary widths.  One rank only (BANN_E_STATE otherwise);
+ * the other errors are bann_init_branches'. */
+int bann_net_init(bann_net* net, const bann_init_cfg* cfg, uint64_t seed);
+/* rs-bann simulate-y (rs-bann.rs:466-501) on the cohort of ctx (NULL: the net's own; another context
+ * as in bann_net_predict): g = Net::predict, summed on the device in net.rs:546-557's order, with
+ * bann_net_predict's bits.  heritability == 1: y = g and the residual variance is 0.  Otherwise
+ * s2 = the sample variance (n - 1) of g in f64 by a fixed-order two-pass reduction,
+ * rv = s2 (1 / h - 1) in f64 and y_i = g_i + (float)(sqrt(rv) z_i), z_i a standard normal that is a
+ * pure function of (seed, i).  stats_out = {mean of y, sample variance of y, rv}, each formed in f64
+ * and cast to f32 (489-501).  Only the n floats of y and the moments leave the device.  BANN_E_ARG
+ * for h outside (0, 1] (the reference's Normal::new(0, inf) panics at 0); BANN_E_SHAPE for n < 2. */
+int bann_net_simulate_y(bann_net* net, bann_ctx* ctx, float heritability, uint64_t seed, float* y_out,
+                        float stats_out[3]);
+/* the BranchCfgs as one serde_json line, the line of outdir/trace: simulate-y's model.params
+ * (rs-bann.rs:460-464) */
+int bann_net_write_params(const bann_net* net, const char* path);
 int bann_net_summary(const bann_net* net, bann_train_summary* out);
 /* the recorded mse_train / lpd series (TrainingStats::mse_train / lpd);
  * writes min(cap, num_records) entries of each (either may be NULL) */

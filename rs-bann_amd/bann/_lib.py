@@ -57,6 +57,13 @@ class McmcCfg(C.Structure):
                 ("gradient_descent_joint", C.c_int32), ("effect_sizes", C.c_int32)]
 
 
+class InitCfg(C.Structure):
+    """bann_init_cfg (the BranchCfgBuilder options behind train-new and simulate-y)"""
+    _fields_ = [("mode", C.c_int32), ("variance", C.c_float), ("gamma_shape", C.c_float),
+                ("gamma_scale", C.c_float), ("num_effective", C.c_int32), ("proportion_effective", C.c_float),
+                ("has_fixed_precision", C.c_int32), ("fixed_precision", C.c_float)]
+
+
 # bann_allreduce_fn: in-place sum over ranks of a host buffer (dtype 0 f32, 1 f64)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 UNIFORM_FN = C.CFUNCTYPE(C.c_double, C.c_void_p)
@@ -177,6 +184,13 @@ SIGNATURES = {
     "bann_gibbs_posterior": (C.c_int, [_P, _pi32, _i32, _pf32, _pf64, _pf64, _pf64]),
     "bann_gibbs_sample_precisions": (C.c_int, [_P, _pi32, _i32, _pf32, _f32, _f32, _u64]),
     "bann_get_params_all": (C.c_int, [_P, _pf32]),
+    # starting a model: the width rules, the device initialisation, simulate-y
+    "bann_arch_layer_widths": (C.c_int, [_i32, _i32, _i32, _i32, _f32, _i32, _i32, _f32, _pi32]),
+    "bann_init_branches": (C.c_int, [_P, _pi32, _i32, C.POINTER(InitCfg), _u64]),
+    "bann_phen_stats_write": (C.c_int, [C.c_char_p, _f32, _f32, _f32]),
+    "bann_net_init": (C.c_int, [_P, C.POINTER(InitCfg), _u64]),
+    "bann_net_simulate_y": (C.c_int, [_P, _P, _f32, _u64, _pf32, _pf32]),
+    "bann_net_write_params": (C.c_int, [_P, C.c_char_p]),
     # model slots: a chain of saved models from one genotype pass
     "bann_models_reserve": (C.c_int, [_P, _i32]),
     "bann_models_capacity": (C.c_int, [_P]),

@@ -272,6 +272,17 @@ class BannContext:
                                                            float(output_precision), float(error_precision),
                                                            int(seed) & 0xFFFFFFFFFFFFFFFF))
 
+    def init_branches(self, cfg=None, seed: int = 0, branches=None):
+        """BranchCfgBuilder::build on the device for the listed branches (None: every branch): the
+        parameter draws, the effective markers and the maximum-likelihood precisions (+inf where a
+        sum of squares is zero); afterwards as if the vectors had gone through set_params and
+        set_precisions.  cfg: an arch.InitConfig (default: weights ~ N(0, 1 / m_b), biases 0)."""
+        from .arch import InitConfig
+        bl = np.ascontiguousarray(range(self.num_branches) if branches is None else branches, dtype=np.int32)
+        c = (cfg if cfg is not None else InitConfig()).to_c()
+        self._check(self._lib.bann_init_branches(self._h, _ptr(bl, C.c_int32), bl.size, C.byref(c),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF))
+
     def get_params_all(self) -> np.ndarray:
         """every branch's param_vec concatenated in branch order: one copy, one wait."""
         out = np.zeros(sum(self.num_params(b) for b in range(self.num_branches)), np.float32)

@@ -96,6 +96,31 @@ class Net:
         self._check(self._lib.bann_net_set_global(self._h, error_precision, output_layer_precision, output_bias,
                                                   output_bias_precision))
 
+    def init(self, cfg=None, seed: int = 0):
+        """BlockNetCfg::build_net (architectures.rs:187-237) on the device: every branch drawn as
+        ``BannContext.init_branches`` does, the joint output-layer precision in every branch, the
+        globals at build_net's values.  cfg: an arch.InitConfig."""
+        from .arch import InitConfig
+        c = (cfg if cfg is not None else InitConfig()).to_c()
+        self._check(self._lib.bann_net_init(self._h, C.byref(c), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def simulate_y(self, heritability: float, seed: int = 0, ctx=None):
+        """rs-bann simulate-y's phenotypes (rs-bann.rs:466-501) on ctx's cohort (default: the net's own):
+        (y, stats) with y = predict + N(0, rv), rv = var(predict) (1 / h - 1), and stats = {"mean",
+        "variance", "env_variance"} of y; h = 1 gives predict's bits and env_variance 0."""
+        c = ctx if ctx is not None else self._ctx
+        y = np.zeros(c.n, np.float32)
+        st = np.zeros(3, np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.bann_net_simulate_y(self._h, self._ctxh(ctx), float(heritability),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, y.ctypes.data_as(fp),
+                                                  st.ctypes.data_as(fp)))
+        return y, {"mean": float(st[0]), "variance": float(st[1]), "env_variance": float(st[2])}
+
+    def write_params(self, path: str):
+        """the BranchCfgs as one JSON line (the line of outdir/trace; simulate-y's model.params)."""
+        self._check(self._lib.bann_net_write_params(self._h, path.encode()))
+
     def train(self, y, cfg: MCMCConfig = MCMCConfig(), outdir: Optional[str] = None):
         v = np.ascontiguousarray(y, dtype=np.float32)
         self._check(self._lib.bann_net_train(self._h, v.ctypes.data_as(C.POINTER(C.c_float)), v.size,

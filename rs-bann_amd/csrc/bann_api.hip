@@ -584,7 +584,8 @@ extern "C" int bann_ctx_destroy(bann_ctx* ctx) {
                   ctx->d_phi, ctx->d_phi0, ctx->d_mphi, ctx->d_ephi, ctx->d_gphi, ctx->d_pidx, ctx->d_ows,
                   ctx->d_netsum, ctx->d_nety, ctx->d_netrss, ctx->d_netpart, ctx->d_ar64, ctx->d_res, ctx->d_upd_cnt,
                   ctx->d_res_part, ctx->d_ones, ctx->d_cm, ctx->d_cm_scale, ctx->d_gsum, ctx->d_gb_shape,
-                  ctx->d_gb_scale, ctx->d_gb_out, ctx->d_gb_prec, ctx->d_gb_list};
+                  ctx->d_gb_scale, ctx->d_gb_out, ctx->d_gb_prec, ctx->d_gb_list, ctx->d_init_prec, ctx->d_init_stat,
+                  ctx->d_init_list, ctx->d_sim_part};
   for (hipEvent_t e : ctx->tm_pool) (void)hipEventDestroy(e);
   clear_graphs(ctx);
   comm_destroy(ctx);

@@ -9,7 +9,11 @@
 //   SNPId2Ix::from_bim, CorrGraph::from_plink_ld      group/centered.rs:15-42, 54-89
 //   CorrGraph::centered_grouping                      group/centered.rs:91-133
 //   MarkerGrouping::to_file                           group/grouping.rs:16-31
+//   BlockNetCfg::add_branch (the width rules)         net/architectures.rs:93-122
+//   PhenStats::to_file                                data/phen_stats.rs:6-24
+#include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -299,5 +303,68 @@ extern "C" int bann_grouping_write(const char* path, int32_t num_groups, const i
   bool ok = true;
   for (int32_t g = 0; g < num_groups && ok; ++g)
     for (int64_t e = offsets[g]; e < offsets[g + 1] && ok; ++e) ok = fprintf(f, "%d\t%d\n", (int)markers[e], (int)g) > 0;
+  return (fclose(f) == 0 && ok) ? BANN_OK : io_fail(BANN_E_ARG, std::string("write failed: ") + path);
+}
+
+// BlockNetCfg::add_branch (architectures.rs:93-122): the hidden width is formed whatever the depth,
+// the summary width derives from it
+extern "C" int bann_arch_layer_widths(int32_t m, int32_t depth, int32_t hidden_rule, int32_t hidden_fixed,
+                                      float hidden_fraction, int32_t summary_rule, int32_t summary_fixed,
+                                      float summary_fraction, int32_t* layer_widths_out) {
+  if (!layer_widths_out) return io_fail(BANN_E_ARG, "bann_arch_layer_widths: null output");
+  if (m < 1 || depth < 0 || depth + 2 > 8) return io_fail(BANN_E_ARG, "bann_arch_layer_widths: m < 1 or depth outside 0..6");
+  // (size_t)((float)a * f).max(1): the f32 product truncated toward zero; a product beyond int32 is refused
+  auto fraction_of = [](int32_t a, float f, int32_t& out) {
+    if (!(f >= 0.f)) return false;
+    const float v = (float)a * f;
+    if (!(v < 2147483648.f)) return false;
+    out = (int32_t)v < 1 ? 1 : (int32_t)v;
+    return true;
+  };
+  int32_t hidden = 0, summary = 0;
+  if (hidden_rule == 0) {
+    if (hidden_fixed < 1) return io_fail(BANN_E_ARG, "bann_arch_layer_widths: fixed hidden width < 1");
+    hidden = hidden_fixed;
+  } else if (hidden_rule != 1 || !fraction_of(m, hidden_fraction, hidden)) {
+    return io_fail(BANN_E_ARG, "bann_arch_layer_widths: unknown hidden rule or bad fraction");
+  }
+  if (summary_rule == 0) {
+    if (summary_fixed < 1)
+      return io_fail(BANN_E_ARG, "bann_arch_layer_widths: a branch cannot have summary layer width 0");
+    summary = summary_fixed;
+  } else if (summary_rule == 1) {
+    summary = hidden;
+  } else if (summary_rule != 2 || !fraction_of(hidden, summary_fraction, summary)) {
+    return io_fail(BANN_E_ARG, "bann_arch_layer_widths: unknown summary rule or bad fraction");
+  }
+  io_err.clear();
+  for (int32_t l = 0; l < depth; ++l) layer_widths_out[l] = hidden;
+  layer_widths_out[depth] = summary;
+  layer_widths_out[depth + 1] = 1;
+  return depth + 2;
+}
+
+// a JSON number that reads back to the same f32: the fewest significant digits that do, with a
+// fraction part or an exponent (serde_json writes floats so); non-finite: null
+static std::string json_f32(float v) {
+  if (!std::isfinite(v)) return "null";
+  char buf[40];
+  for (int p = 1; p <= 9; ++p) {
+    snprintf(buf, sizeof(buf), "%.*g", p, (double)v);
+    if (strtof(buf, nullptr) == v) break;
+  }
+  std::string s(buf);
+  if (s.find_first_of(".e") == std::string::npos) s += ".0";
+  return s;
+}
+
+extern "C" int bann_phen_stats_write(const char* path, float mean, float variance, float env_variance) {
+  if (!path) return io_fail(BANN_E_ARG, "bann_phen_stats_write: null path");
+  FILE* f = fopen(path, "wb");
+  if (!f) return io_fail(BANN_E_ARG, std::string("cannot open ") + path);
+  const std::string text = "{\n  \"mean\": " + json_f32(mean) + ",\n  \"variance\": " + json_f32(variance) +
+                           ",\n  \"env_variance\": " + json_f32(env_variance) + "\n}";
+  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+  io_err.clear();
   return (fclose(f) == 0 && ok) ? BANN_OK : io_fail(BANN_E_ARG, std::string("write failed: ") + path);
 }

@@ -35,6 +35,10 @@ int residual_from_target_shift(bann_ctx* ctx, int32_t b, float add, double* sum,
 int hmc_step_tail(bann_ctx* ctx, int32_t b, int32_t L, float max_dh, int32_t step_mode, float factor, const float* eps,
                   const float* momentum, uint64_t seed, const float* u, float add, int32_t* status_out,
                   float* params_out, double* stats);
+// kernels_init.hip (library-internal): bann_init_branches over every branch with the joint output-layer
+// precision; the phenotypes of simulate-y at the context's parameters
+int init_branches_net(bann_ctx* ctx, const bann_init_cfg* cfg, uint64_t seed, double* reg_sum_out);
+int simulate_y_device(bann_ctx* ctx, float bias, float heritability, uint64_t seed, float* y_out, float stats_out[3]);
 
 namespace {
 
@@ -1291,9 +1295,10 @@ extern "C" int bann_net_perturb(bann_net* t, int32_t has_params, float params_by
   return BANN_OK;
 }
 
-extern "C" int bann_net_predict(bann_net* t, bann_ctx* ctx, float* y_hat) {
-  if (!t || !y_hat) return BANN_E_ARG;
-  bann_ctx* c = ctx ? ctx : t->ctx;
+namespace {
+// Net::predict's cohort: c holds the net's branches (count, markers, layer widths); another context
+// than the net's own receives the net's current parameters
+int predict_context(bann_net* t, bann_ctx* c) {
   const int nb = (int)t->br.size();
   if (bann_num_branches(c) != nb) return fail(t, BANN_E_SHAPE, "context branch count differs from the net");
   for (int b = 0; b < nb; ++b) {
@@ -1302,18 +1307,26 @@ extern "C" int bann_net_predict(bann_net* t, bann_ctx* ctx, float* y_hat) {
         L != t->br[b].L || L > BANN_NET_MAXL || !std::equal(w, w + L, t->br[b].widths.begin()))
       return fail(t, BANN_E_SHAPE, "context branches differ from the net's");
   }
-  const int64_t nt = bann_ctx_num_individuals(c);
-  if (nt <= 0) return fail(t, BANN_E_STATE, "context has no cohort");
-  std::vector<int32_t> all(nb);
-  for (int b = 0; b < nb; ++b) {
-    all[b] = b;
-    if (c != t->ctx) {
-      const int rc = bann_branch_set_params(c, b, t->br[b].params.data());
-      if (rc < 0) return fail(t, rc, std::string("predict context: ") + bann_last_error(c));
-    }
+  if (bann_ctx_num_individuals(c) <= 0) return fail(t, BANN_E_STATE, "context has no cohort");
+  for (int b = 0; b < nb && c != t->ctx; ++b) {
+    const int rc = bann_branch_set_params(c, b, t->br[b].params.data());
+    if (rc < 0) return fail(t, rc, std::string("predict context: ") + bann_last_error(c));
   }
+  return BANN_OK;
+}
+}  // namespace
+
+extern "C" int bann_net_predict(bann_net* t, bann_ctx* ctx, float* y_hat) {
+  if (!t || !y_hat) return BANN_E_ARG;
+  bann_ctx* c = ctx ? ctx : t->ctx;
+  const int nb = (int)t->br.size();
+  int rc = predict_context(t, c);
+  if (rc) return rc;
+  const int64_t nt = bann_ctx_num_individuals(c);
+  std::vector<int32_t> all(nb);
+  for (int b = 0; b < nb; ++b) all[b] = b;
   std::vector<float> preds((size_t)nb * nt);
-  const int rc = bann_predict_many(c, all.data(), nb, preds.data());
+  rc = bann_predict_many(c, all.data(), nb, preds.data());
   if (rc < 0) return fail(t, rc, std::string("predict: ") + bann_last_error(c));
   for (int64_t i = 0; i < nt; ++i) {  // y_hat = 0 + bias, then += f_b in branch order (f32, net.rs:546-557)
     float v = 0.f + t->ob_bias;
@@ -1321,6 +1334,59 @@ extern "C" int bann_net_predict(bann_net* t, bann_ctx* ctx, float* y_hat) {
     y_hat[i] = v;
   }
   return BANN_OK;
+}
+
+// BlockNetCfg::build_net (architectures.rs:187-237) over the net's context: every branch initialised on
+// the device with the joint output-layer precision, the host BranchCfgs refreshed from it, the globals
+extern "C" int bann_net_init(bann_net* t, const bann_init_cfg* cfg, uint64_t seed) {
+  if (!t || !cfg) return t ? fail(t, BANN_E_ARG, "null configuration") : BANN_E_ARG;
+  int32_t nranks = 1;
+  CKB(bann_comm_info(t->ctx, nullptr, &nranks, nullptr, nullptr));
+  if (nranks > 1) return fail(t, BANN_E_STATE, "bann_net_init runs on one rank (the joint output precision has no all-reduce)");
+  double reg = 0.0;
+  CKB(init_branches_net(t->ctx, cfg, seed, &reg));
+  int64_t total = 0;
+  for (const Branch& B : t->br) total += B.P;
+  std::vector<float> theta((size_t)total);
+  CKB(bann_get_params_all(t->ctx, theta.data()));
+  int64_t o = 0;
+  uint64_t num = 0;
+  for (size_t b = 0; b < t->br.size(); ++b) {
+    Branch& B = t->br[b];
+    std::copy(theta.begin() + o, theta.begin() + o + B.P, B.params.begin());
+    o += B.P;
+    CKB(bann_branch_get_precisions(t->ctx, (int32_t)b, B.prec.data()));
+    num += (uint64_t)B.win[B.L - 1];
+  }
+  t->g_reg_sum = (float)reg;
+  t->g_num = num;
+  // GlobalParams and OutputBias of build_net (216-236)
+  return bann_net_set_global(t, 2.f, cfg->has_fixed_precision ? cfg->fixed_precision : 0.05f, 0.f, 1.f);
+}
+
+// rs-bann simulate-y (rs-bann.rs:466-501) on the cohort of ctx
+extern "C" int bann_net_simulate_y(bann_net* t, bann_ctx* ctx, float heritability, uint64_t seed, float* y_out,
+                                   float stats_out[3]) {
+  if (!t || !y_out || !stats_out) return t ? fail(t, BANN_E_ARG, "null output") : BANN_E_ARG;
+  if (!(heritability > 0.f && heritability <= 1.f))
+    return fail(t, BANN_E_ARG, "heritability must be in (0, 1]");
+  bann_ctx* c = ctx ? ctx : t->ctx;
+  if (bann_ctx_num_individuals(c) == 1) return fail(t, BANN_E_SHAPE, "a sample variance needs at least two individuals");
+  int rc = predict_context(t, c);
+  if (rc) return rc;
+  rc = simulate_y_device(c, t->ob_bias, heritability, seed, y_out, stats_out);
+  if (rc < 0) return fail(t, rc, std::string("simulate_y: ") + bann_last_error(c));
+  return BANN_OK;
+}
+
+extern "C" int bann_net_write_params(const bann_net* t, const char* path) {
+  if (!t || !path) return BANN_E_ARG;
+  bann_net* m = const_cast<bann_net*>(t);
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return fail(m, BANN_E_ARG, std::string("cannot open ") + path);
+  const std::string text = trace_line(t);
+  const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
+  return (std::fclose(f) == 0 && ok) ? BANN_OK : fail(m, BANN_E_ARG, std::string("short write to ") + path);
 }
 
 namespace {

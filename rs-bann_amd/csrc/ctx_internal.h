@@ -197,6 +197,11 @@ struct bann_ctx {
   double* d_gb_out = nullptr;    // [nbranch]: the output-weight statistic
   float* d_gb_prec = nullptr;    // [total_q]: the drawn precision vectors (the host mirrors' source)
   int32_t* d_gb_list = nullptr;  // [nbranch]: the listed branches
+  // the model initialisation and the phenotype simulation (kernels_init.hip), allocated at their first call
+  float* d_init_prec = nullptr;   // [total_q]: the initial precision vectors (the host mirrors' source)
+  double* d_init_stat = nullptr;  // [nbranch][2] + 2: per branch sum w_out^2 and summary_stat_fn(w_out), then their sums
+  int32_t* d_init_list = nullptr; // [nbranch]: the listed branches
+  double* d_sim_part = nullptr;   // block partials of the phenotype moments, then the folded sums (sim_part_doubles)
   // the LD graph of the last bann_genotypes_ld_graph call (bann_ld.hip): symmetric CSR, kept on the host
   std::vector<int64_t> ld_off;
   std::vector<int32_t> ld_nb;
@@ -288,6 +293,13 @@ int residual_from_target_shift_launch(bann_ctx* ctx, int32_t b, float add);
 int hmc_step_tail(bann_ctx* ctx, int32_t b, int32_t L, float max_dh, int32_t step_mode, float factor, const float* eps,
                   const float* momentum, uint64_t seed, const float* u, float add, int32_t* status_out,
                   float* params_out, double* stats);
+// kernels_init.hip (library-internal, for bann_net.cpp): bann_init_branches over every branch with the
+// joint output-layer precision nb / sum_b sum w_out,b^2 in every branch's output-layer entry (the fixed
+// precision when there is one); reg_sum_out = sum_b summary_stat_fn(w_out,b), branch order, f64
+int init_branches_net(bann_ctx* ctx, const bann_init_cfg* cfg, uint64_t seed, double* reg_sum_out);
+// g = (0 + bias) + sum_b f_b in branch order (f32) at the context's parameters, y = g + noise, the
+// moments; bann_net_simulate_y without the net (include/bann_net.h)
+int simulate_y_device(bann_ctx* ctx, float bias, float heritability, uint64_t seed, float* y_out, float stats_out[3]);
 int net_buffers_init(bann_ctx* ctx);
 // network mode: k_forward_gsum's items for a persistent fx-only plan of 8-chunk branches
 int build_net_groups(bann_ctx* ctx, Plan& p);

@@ -23,6 +23,7 @@
 
 #include "ctx_internal.h"
 #include "gibbs_gamma.h"
+#include "prec_expand.h"
 
 #define GIBBS_THREADS 256
 
@@ -155,18 +156,7 @@ __global__ __launch_bounds__(GIBBS_THREADS) void k_gibbs_draw(
   }
   if (t == 0) ep[b] = eprec;
   __syncthreads();  // the workgroup's own global writes are visible to it
-  // expand_precisions and step_bases (bann_api.hip): ridge / bias pi / (2 sqrt(lam)), lasso 1 / (4 lam)
-  const bool lasso = d.prior == BANN_LASSO_ARD || d.prior == BANN_LASSO_BASE;
-  const double PI = 3.14159265358979323846;
-  const int nweights = d.boff[0];
-  for (int p = t; p < d.P; p += GIBBS_THREADS) {
-    const float v = pq[pidx[d.p_off + p]];
-    const bool weight = p < nweights;  // the biases carry no prior term in the density (branch_sampler.rs:106-112)
-    lam[d.p_off + p] = weight ? v : 0.f;
-    lamld[d.p_off + p] = weight ? v : 0.f;
-    const double lv = (double)v;
-    sbase[d.p_off + p] = (lasso && weight) ? 1.0 / (4.0 * lv) : PI / (2.0 * sqrt(lv));
-  }
+  expand_branch_precisions(d, pq, pidx, lam, lamld, sbase, t, GIBBS_THREADS);
 }
 
 // the Gibbs scratch of a context, allocated at the first call: (shape, scale) and the compact
