@@ -675,6 +675,13 @@ int bann_get_graph_replay(const bann_ctx* ctx);
 int bann_set_fused_enabled(bann_ctx* ctx, int32_t enabled);
 /* bytes of packed genotype data read per full gradient evaluation of all branches */
 int64_t bann_packed_genotype_bytes(const bann_ctx* ctx);
+/* diagnostic of the fx stream's addressing on the current device: a one-wave LDS-DMA copy
+ * whose four pieces differ only in the instruction's immediate offset.  *lds_follows = 1 if
+ * the offset advanced the LDS address as well as the global one, 0 if the global one alone
+ * (-1: neither pattern); *built_mode = how this library's steady fx tiles address their
+ * pieces (0 full address and M0 per piece, 2 immediate offset for both addresses: needs
+ * *lds_follows = 1) */
+int bann_fx_dma_offset_probe(int32_t* lds_follows, int32_t* built_mode);
 
 #ifdef __cplusplus
 }

@@ -207,6 +207,7 @@ SIGNATURES = {
     "bann_set_fused_enabled": (C.c_int, [_P, _i32]),
     "bann_set_hidden_gemm_bf16": (C.c_int, [_P, _i32]),
     "bann_packed_genotype_bytes": (_i64, [_P]),
+    "bann_fx_dma_offset_probe": (C.c_int, [_pi32, _pi32]),
     # bann_net.h: the Net::train driver and the Net<B> model file
     "bann_net_create": (C.c_int, [_P, C.POINTER(PrecisionHyperparams), _u64, C.POINTER(_P)]),
     "bann_net_destroy": (C.c_int, [_P]),

@@ -68,6 +68,40 @@ __device__ __forceinline__ void glds16_s(const void* sbase, uint32_t voff, const
                : "memory", "m0");
 #endif
 }
+// the saddr form with an immediate byte offset OFF (0 .. 4095) and M0 as an operand: the
+// compiler writes M0 only where its value changes, so pieces that share an LDS base and a
+// 64-bit global base differ in OFF alone.  The hardware adds OFF to BOTH addresses (global
+// and M0's LDS base: tests/test_fx_steady_loop_gpu.py probes it), which an HBM image laid out
+// like its LDS image wants.  The s_nop covers an M0 write in the instruction just before.
+template <int OFF>
+__device__ __forceinline__ void glds16_so(const void* sbase, uint32_t voff, uint32_t m0v) {
+  static_assert(OFF >= 0 && OFF < 4096, "13-bit signed immediate, used non-negative");
+#if BANN_GLDS_NT
+  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%c2 nt" ::"v"(voff), "s"(sbase), "n"(OFF), "{m0}"(m0v)
+               : "memory");
+#else
+  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%c2" ::"v"(voff), "s"(sbase), "n"(OFF), "{m0}"(m0v)
+               : "memory");
+#endif
+}
+// the same for the lanes of `mask` only (nonzero), without a branch around it: exec is
+// narrowed and restored inside the statement
+template <int OFF>
+__device__ __forceinline__ void glds16_so_masked(const void* sbase, uint32_t voff, uint32_t m0v, uint64_t mask) {
+  static_assert(OFF >= 0 && OFF < 4096, "13-bit signed immediate, used non-negative");
+  uint64_t keep;
+#if BANN_GLDS_NT
+  asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %5\n\tglobal_load_lds_dwordx4 %1, %2 offset:%c3 nt\n\ts_mov_b64 exec, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(sbase), "n"(OFF), "{m0}"(m0v), "s"(mask)
+               : "memory");
+#else
+  asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %5\n\tglobal_load_lds_dwordx4 %1, %2 offset:%c3\n\ts_mov_b64 exec, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(sbase), "n"(OFF), "{m0}"(m0v), "s"(mask)
+               : "memory");
+#endif
+}
 __device__ __forceinline__ void glds4(const void* gsrc, const void* lds_dst) {
   const uint32_t m0 = __builtin_amdgcn_readfirstlane(lds_off(lds_dst));
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" ::"s"(m0), "v"(gsrc) : "memory", "m0");

@@ -41,6 +41,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
+#include "../../include/bann.h"
 #include "activations.h"
 #include "bann_internal.h"
 #include "fx_shapes.h"
@@ -81,6 +82,38 @@
 #endif
 #ifndef FX_ABL
 #define FX_ABL 0
+#endif
+// FX_STEADY 1: k_fused_grad_fx runs its tiles from two loops over one body.  A tile whose successor
+// two rounds on (tile tt + 2 NW, refilled into its slot) exists and is full, in a launch that writes no
+// predictions, takes the steady instantiation: no more / more2 / valid / write_pred guards, a constant
+// vmcnt, an unclamped target row -- its backward is one basic block.  Every other tile (a wave's last
+// two, a partial last tile, a prediction-writing launch) takes the guarded one.  Same tile order, same
+// accumulation order: bit-identical outputs.  0: the guarded body alone, the loop as it was
+// (tools/build_ab.sh <tag> "-DFX_STEADY=0" kernels_fx for A/B runs and bit comparisons).
+// FX_DMA_IMM (steady tiles): 0 = every stream piece forms its 64-bit address and writes M0;
+// 2 = two 64-bit bases per tile, the piece as the instruction's immediate offset, which gfx950 adds to
+// the LDS address too (bann_fx_dma_offset_probe), so M0 is written once per 4 KiB half slot.  (1 would
+// be the offset on the global address alone with M0 per piece: wrong on this hardware, not built.)
+// On its own it costs 0.5 - 1 % per launch, but without it the two bodies spill vector registers
+// in every instantiation but the tanh one.
+// FX_RFB: the delta0 scale's two fallback forms (unset -> 5 / 255) live in registers, updated only in
+// the rare rescale path, instead of two selects per column and tile.
+#ifndef FX_STEADY
+#define FX_STEADY 1
+#endif
+#ifndef FX_DMA_IMM
+#define FX_DMA_IMM (FX_STEADY ? 2 : 0)
+#endif
+#if FX_DMA_IMM != 0 && FX_DMA_IMM != 2
+#error "FX_DMA_IMM: 0 or 2"
+#endif
+#ifndef FX_RFB
+#define FX_RFB FX_STEADY
+#endif
+// beside the steady body the guarded one (a wave's last two tiles) reads fewer backward windows
+// ahead: the two bodies' loop-invariant values together would otherwise spill vector registers
+#ifndef FXT_PD_EDGE
+#define FXT_PD_EDGE 4  // 8 spills 2 .. 5 vector registers in the ReLU / leaky / SiLU / identity instantiations
 #endif
 #if FX_STAMPS
 #define FX_STAMP(i)                                            \
@@ -279,6 +312,39 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
     const int64_t row = 64 * (int64_t)tt + iota;
     glds4(ybr + (row < n ? row : n - 1), &s_y[wave][sl][0]);
   };
+#if FX_STEADY
+  auto issue_y_full = [&](int tt, int sl) {  // a full tile: no row clamp
+    if (FX_ABL & 16) return;
+    glds4(ybr + (64 * (int64_t)tt + iota), &s_y[wave][sl][0]);
+  };
+#if FX_DMA_IMM
+  // piece c of the tile image at nb into the slot at LDS byte address lb (both wave-uniform):
+  // HBM image == LDS image, so the halves' bases and the immediate offset address both
+  const uint64_t live_rows = __builtin_amdgcn_ballot_w64(!pad_row);  // the last chunk's streamed rows
+  auto issue_piece = [&](const char* nb, uint32_t lb, int c) __attribute__((always_inline)) {
+    if (FX_ABL & 16) return;
+    const char* gb = nb + 4096 * (c >> 2);
+    const uint32_t voff = (uint32_t)lane * 16u;
+    const uint32_t m0v = lb + 4096u * (uint32_t)(c >> 2);
+    if (NCH != 0 && c != NCH - 1) {
+      switch (c & 3) {
+        case 0: glds16_so<0>(gb, voff, m0v); break;
+        case 1: glds16_so<1024>(gb, voff, m0v); break;
+        case 2: glds16_so<2048>(gb, voff, m0v); break;
+        default: glds16_so<3072>(gb, voff, m0v); break;
+      }
+    } else {  // the last chunk's padding rows are not streamed: exec-masked, as in issue_chunk
+      const uint64_t mk = (NCH != 0 || c == nch - 1) ? live_rows : ~0ull;
+      switch (c & 3) {
+        case 0: glds16_so_masked<0>(gb, voff, m0v, mk); break;
+        case 1: glds16_so_masked<1024>(gb, voff, m0v, mk); break;
+        case 2: glds16_so_masked<2048>(gb, voff, m0v, mk); break;
+        default: glds16_so_masked<3072>(gb, voff, m0v, mk); break;
+      }
+    }
+  };
+#endif
+#endif
   // the item's first two tiles are issued before the prologue's loads, so their HBM latency
   // overlaps the W0-digit and head-weight loads (a solo item -- the sequential driver's
   // one-branch steps -- has one tile per wave: the launch was that latency longer)
@@ -358,16 +424,28 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
   const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime(), mt0 = __builtin_amdgcn_s_memtime();
   unsigned long long t_last = mt0;
 #endif
-  for (; tt < te; tt += NW, sl ^= 1) {
-    const bool more = tt + NW < te;
-    const bool more2 = tt + 2 * NW < te;  // tile tt + 2 NW goes into this slot
+#if FX_RFB
+  int Rg[4] = {5, 5, 5, 5};          // R[k] ? R[k] : 5, the growth test's threshold
+  int Rd[4] = {255, 255, 255, 255};  // R[k] ? R[k] : 255, the digit exponent's
+#endif
+  // one tile; ST (FX_STEADY): the steady instantiation, whose guards are compile-time true / false
+#if FX_STEADY
+  auto tile = [&](auto steady_c) __attribute__((always_inline)) {
+    constexpr bool ST = decltype(steady_c)::value;
+#else
+  for (; tt < te; tt += NW, sl ^= 1) {  // the body below, as the loop it was
+    constexpr bool ST = false;
+#endif
+    const bool more = ST || tt + NW < te;
+    const bool more2 = ST || tt + 2 * NW < te;  // tile tt + 2 NW goes into this slot
+    const bool wpred = !ST && write_pred;
     // tile tt (issued during tile tt - NW) has landed.  (An L2 prefetch of the
     // tile after it measured +3 %: with 8 waves/CU the L2 is already the DMA's
     // working set.)
     // the nch + 1 pieces of tile tt + NW are younger (loads return in order; a
     // younger pred store still outstanding only makes this wait longer)
     FX_STAMP(5);
-    vm_wait(more ? nch + 1 : 0);
+    vm_wait(more ? nch + 1 : 0);  // steady, NCH = 8: the constant vmcnt(9)
     FX_STAMP(0);
     const char* xs = &s_x[wave][sl][0];
 
@@ -434,12 +512,12 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
 
     // ---- head: one individual per lane ----
     const int64_t row = 64 * (int64_t)tt + iota;
-    const bool valid = row < n;
+    const bool valid = ST || row < n;
     const float yv = s_y[wave][sl][lane];
     float d[4];
 #if FX_ABL & 4
     d[0] = z0 + yv, d[1] = z1, d[2] = z2, d[3] = z3;
-    if (write_pred && valid) predb[row] = z0;
+    if (wpred && valid) predb[row] = z0;
     rss += (double)z1;
 #else
     {
@@ -467,7 +545,7 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
 #pragma unroll
       for (int j = 0; j < 4; ++j) out = fmaf(a[NH - 1][j], Wh[NL - 1][j][0], out);
       const float e = valid ? (net_err ? yv : out - yv) : 0.f;
-      if (write_pred && valid) predb[row] = out;
+      if (wpred && valid) predb[row] = out;
       rss += (double)e * (double)e;
       float err[4];
 #pragma unroll
@@ -504,12 +582,22 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
 
     if (more2) {  // the target has been read (yv in a register): its slot takes tile tt + 2 NW's
       asm volatile("" ::"v"(yv));
-      issue_y(tt + 2 * NW, sl);
+#if FX_STEADY
+      if (ST)
+        issue_y_full(tt + 2 * NW, sl);
+      else
+#endif
+        issue_y(tt + 2 * NW, sl);
     }
+#if FX_STEADY && FX_DMA_IMM
+    // the refill's two wave-uniform bases, once per tile
+    const char* const nb = xbase_s + (uint64_t)(tt + 2 * NW) * (uint64_t)tile_bytes;
+    const uint32_t lb = __builtin_amdgcn_readfirstlane(lds_off(&s_x[wave][sl][0]));
+#endif
     __builtin_amdgcn_sched_barrier(0);
     FX_STAMP(2);
     // the backward's first genotype windows: their LDS reads fly under the digit phase
-    constexpr int PD = FXT_PD;
+    constexpr int PD = ST || !FX_STEADY ? FXT_PD : FXT_PD_EDGE;
     uint32_t wq[PD];
 #pragma unroll
     for (int u = 0; u < PD; ++u)
@@ -525,7 +613,11 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int ek = (int)((fbits(d[k]) >> 23) & 0xFFu);
+#if FX_RFB
+        lane_need |= ek > Rg[k];
+#else
         lane_need |= ek > (R[k] ? R[k] : 5);
+#endif
       }
       if (__builtin_amdgcn_ballot_w64(lane_need) != 0) {
         const uint32_t e01 = wave_max_u16x2(((fbits(d[0]) >> 23) & 0xFFu) | (((fbits(d[1]) >> 23) & 0xFFu) << 16));
@@ -533,6 +625,16 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
         const int E[4] = {(int)(e01 & 0xFFFFu), (int)(e01 >> 16), (int)(e23 & 0xFFFFu), (int)(e23 >> 16)};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
+#if FX_RFB
+          // the same test on the threshold: 5 while unset (E >= 6), R >= 8 once set (E > R)
+          if (E[k] > Rg[k]) {
+            if (Rg[k] != 5) {
+              dl[k] = E[k] + 2 - Rg[k];
+              grow = true;
+            }
+            Rg[k] = Rd[k] = E[k] + 2;
+          }
+#else
           if (E[k] >= 6 && (R[k] == 0 || E[k] > R[k])) {  // first scale, or |delta| outgrew it
             if (R[k] != 0) {
               dl[k] = E[k] + 2 - R[k];
@@ -540,6 +642,7 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
             }
             R[k] = E[k] + 2;
           }
+#endif
         }
       }
     }
@@ -554,8 +657,13 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
     // this lane's individual sits in K-group p = g of the backward operand, whose
     // genotype codes stay in place (x 4^p): pre-divide its digits by 4^p
     const int kslot_sh = 2 * g;
+#if FX_RFB
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = digits4_fx(d[k], 153 - kslot_sh - Rd[k]);
+#else
 #pragma unroll
     for (int k = 0; k < 4; ++k) w[k] = digits4_fx(d[k], 153 - kslot_sh - (R[k] ? R[k] : 255));
+#endif
     *reinterpret_cast<v4u*>(sd_w) = w;
 
     __builtin_amdgcn_sched_barrier(0);
@@ -584,7 +692,12 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
         if (u + 2 < 32 && (NCH != 0 || u + 2 < 4 * nch)) Bn2 = unpack(wq[(u + 2) % PD]);
         if (more2 && (u & 3) == 1) {  // window 4c + 3, chunk c's last, is unpacked: refill chunk c
           asm volatile("" ::"v"(Bn2[0]), "v"(Bn2[1]), "v"(Bn2[2]), "v"(Bn2[3]));
-          issue_chunk(tt + 2 * NW, sl, u >> 2);
+#if FX_STEADY && FX_DMA_IMM
+          if (ST)
+            issue_piece(nb, lb, u >> 2);
+          else
+#endif
+            issue_chunk(tt + 2 * NW, sl, u >> 2);
         }
         if (u + PD < 32 && (NCH != 0 || u + PD < 4 * nch))  // slot of window u, consumed two iterations ago
           wq[u % PD] = *reinterpret_cast<const uint32_t*>(xs + 256 * (u + PD) + (((u + PD) & 1) ? boo : boe));
@@ -595,7 +708,23 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
 #if FX_STAMPS
     ++ntl;
 #endif
+#if FX_STEADY
+  };
+  {
+    // steady tiles: tile tt + 2 NW exists and is full (so is tile tt: its target row needs no
+    // clamp either), no prediction store
+    const int64_t t_full = (n >> 6) - 2 * NW, t_more = (int64_t)te - 2 * NW;
+    const int t_st = write_pred ? tt : (int)(t_full < t_more ? t_full : t_more);
+    for (; tt < t_st; tt += NW, sl ^= 1) tile(std::true_type{});
   }
+  for (; tt < te; tt += NW, sl ^= 1) tile(std::false_type{});
+#else
+  }
+#endif
+#if FX_RFB
+#pragma unroll
+  for (int k = 0; k < 4; ++k) R[k] = Rg[k] != 5 ? Rg[k] : 0;
+#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if FX_STAMPS
   ph[6] = __builtin_amdgcn_s_memrealtime() - rt0;
@@ -771,6 +900,49 @@ void launch_fused_grad_fx(const DevState& st, const GradItem* items, int32_t nit
     case 9: launch_fx_nl<4, 8>(st, items, nitems, act, wp, um, us, upd_cnt, fo, s); break;
     default: break;
   }
+}
+
+// Does the immediate offset of global_load_lds_dwordx4 advance the LDS address (M0's base) as well
+// as the global one?  One wave copies 4 KiB as four pieces that differ in the offset alone (0, 1024,
+// 2048, 3072; one M0) into a 4 KiB array preset to 0xFF, then the array goes out to dst.
+__global__ void __launch_bounds__(64) k_glds_offset_probe(const char* __restrict__ src, uint32_t* __restrict__ dst) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_p[1024];
+  for (int i = threadIdx.x; i < 1024; i += 64) s_p[i] = 0xFFFFFFFFu;
+  __syncthreads();
+  const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds_off(&s_p[0]));
+  const uint32_t voff = threadIdx.x * 16u;
+  glds16_so<0>(src, voff, m0v);
+  glds16_so<1024>(src, voff, m0v);
+  glds16_so<2048>(src, voff, m0v);
+  glds16_so<3072>(src, voff, m0v);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int i = threadIdx.x; i < 1024; i += 64) dst[i] = s_p[i];
+}
+
+extern "C" int bann_fx_dma_offset_probe(int32_t* lds_follows, int32_t* built_mode) {
+  if (!lds_follows || !built_mode) return BANN_E_ARG;
+  *built_mode = FX_STEADY ? FX_DMA_IMM : 0;
+  *lds_follows = -1;
+  uint32_t h_src[1024], h_dst[1024];
+  for (int i = 0; i < 1024; ++i) h_src[i] = 0x9E3779B1u * (uint32_t)(i + 1) & 0x7FFFFFFFu;  // never 0xFFFFFFFF
+  void *d_src = nullptr, *d_dst = nullptr;
+  bool ok = hipMalloc(&d_src, 4096) == hipSuccess && hipMalloc(&d_dst, 4096) == hipSuccess &&
+            hipMemcpy(d_src, h_src, 4096, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_glds_offset_probe, dim3(1), dim3(64), 0, nullptr, (const char*)d_src, (uint32_t*)d_dst);
+    ok = hipGetLastError() == hipSuccess && hipMemcpy(h_dst, d_dst, 4096, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  if (d_src) (void)hipFree(d_src);
+  if (d_dst) (void)hipFree(d_dst);
+  if (!ok) return BANN_E_HIP;
+  bool both = true, global_only = true;  // global only: the pieces land on each other, the last one stays
+  for (int i = 0; i < 1024; ++i) {
+    both = both && h_dst[i] == h_src[i];
+    global_only = global_only && h_dst[i] == (i < 256 ? h_src[768 + i] : 0xFFFFFFFFu);
+  }
+  *lds_follows = both ? 1 : global_only ? 0 : -1;
+  return BANN_OK;
 }
 
 // ===========================================================================
