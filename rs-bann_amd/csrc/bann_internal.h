@@ -255,11 +255,20 @@ void launch_pack_fi(const uint8_t* raw, int64_t rowb, const PackJob* jobs, int32
 // model slots (bann_models_*), each with its own parameters, W0 digits and fused constants;
 // model j writes the row of branch b at pred[j] + BranchDev::y_off
 #define BANN_FE_KM 4  // models per genotype pass
-struct FeModels {
-  int32_t nk;  // models of this pass, 1 .. BANN_FE_KM
-  const float* theta[BANN_FE_KM];
-  const uint8_t* dig[BANN_FE_KM];
-  const FusedConst* fc[BANN_FE_KM];
+// what the shared tile pass (fe_stream.h) reads of the models of one pass
+template <int KM>
+struct FeModelSet {
+  int32_t nk;  // models of this pass, 1 .. KM
+  const float* theta[KM];
+  const uint8_t* dig[KM];
+  const FusedConst* fc[KM];
+  // unused models: model 0's pointers (the kernels' prologue reads every model)
+  void fill_unused() {
+    for (int k = nk; k < KM; ++k) theta[k] = theta[0], dig[k] = dig[0], fc[k] = fc[0];
+  }
+};
+static_assert(sizeof(FeModelSet<3>) == 8 + 3 * 24, "kernel argument: nk, then the three pointer arrays, no tail");
+struct FeModels : FeModelSet<BANN_FE_KM> {
   float* pred[BANN_FE_KM];
   float bias[BANN_FE_KM];  // output bias (launch_models_sum)
 };
@@ -276,12 +285,7 @@ void launch_models_moments(const float* rows, int32_t nk, int64_t n, float* mean
 #ifndef BANN_FS_KM
 #define BANN_FS_KM 3  // models per genotype pass (register budget: DESIGN.md 4.8)
 #endif
-struct FsModels {
-  int32_t nk;  // models of this pass, 1 .. BANN_FS_KM
-  const float* theta[BANN_FS_KM];
-  const uint8_t* dig[BANN_FS_KM];
-  const FusedConst* fc[BANN_FS_KM];
-};
+struct FsModels : FeModelSet<BANN_FS_KM> {};
 void launch_stats_fe(const DevState& st, const FsModels& mm, const GradItem* items, int32_t nitems, int32_t L,
                      int32_t act, const float* y, double* part, int64_t model_stride, hipStream_t s);
 // one listed fx branch: its records (item_begin .. + item_count in the call's item order) and where

@@ -34,34 +34,13 @@
 
 #include "activations.h"
 #include "bann_internal.h"
-#include "kernel_util.h"
+#include "fe_util.h"
 
 #define FI_WAVES 4
 #define FI_MAXSEG 2  // m_b <= 512
 #ifndef FI_NT
 #define FI_NT 1  // non-temporal loads: the image is read once per pass
 #endif
-
-typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float fi_comb4(v4i d) {  // sum_d D_d 2^(-7 d)
-  return (float)d[0] + (float)d[1] * 0x1p-7f + (float)d[2] * 0x1p-14f + (float)d[3] * 0x1p-21f;
-}
-__device__ __forceinline__ void fi_swap32(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                                  false, false);
-  a = __builtin_bit_cast(float, (unsigned)r[0]);
-  b = __builtin_bit_cast(float, (unsigned)r[1]);
-}
-__device__ __forceinline__ void fi_swap16(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                                  false, false);
-  a = __builtin_bit_cast(float, (unsigned)r[0]);
-  b = __builtin_bit_cast(float, (unsigned)r[1]);
-}
-__device__ __forceinline__ float fi_uni(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
 
 // tiles of a work item (64-individual tiles, frag ranges on tile boundaries)
 __device__ __forceinline__ int32_t fi_tiles(const GradItem& it) { return ((it.frag_end + 3) >> 2) - (it.frag_begin >> 2); }
@@ -116,14 +95,14 @@ __device__ __forceinline__ void fi_load_branch(const DevState& st, int b, int la
       for (int k = 0; k < 4; ++k) {
         float v = 0.f;
         if (l >= 1 && (l < NL - 1 || k == 0) && j < bd.win[l] && k < bd.widths[l]) v = th[bd.woff[l] + k * bd.win[l] + j];
-        c.W[l][j][k] = fi_uni(v);
+        c.W[l][j][k] = sgpr_f(v);
       }
     if (l < NL - 1)
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float v = 0.f;
         if (k < bd.widths[l]) v = l == 0 ? st.fc[b].c0[k] : th[bd.boff[l] + k];
-        c.B[l][k] = fi_uni(v);
+        c.B[l][k] = sgpr_f(v);
       }
   }
   c.x = reinterpret_cast<const char*>(st.xi) + bd.xi_off + lane * 16;
@@ -161,13 +140,13 @@ __device__ __forceinline__ void fi_tile(const FiBranch<NL>& c, const v4u (&X)[4]
     }
     // value x 16 = 16 acc0 + 4 acc1 + acc2 + acc3, per digit, exact in int32
     const v4i D = acc[0] * 16 + acc[1] * 4 + acc[2] + acc[3];
-    z[f] = c.zs * fi_comb4(D);  // lane (g, i): column g of individual 16 f + i
+    z[f] = c.zs * comb4(D);  // lane (g, i): column g of individual 16 f + i
   }
   // transpose (frag, lane group) -> (column, lane group): lane L = individual L of the tile
-  fi_swap32(z[0], z[2]);
-  fi_swap32(z[1], z[3]);
-  fi_swap16(z[0], z[1]);
-  fi_swap16(z[2], z[3]);
+  swap32(z[0], z[2]);
+  swap32(z[1], z[3]);
+  swap16(z[0], z[1]);
+  swap16(z[2], z[3]);
   float a[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) a[k] = act_h_t<ACT>(z[k] + c.B[0][k]);

@@ -1,16 +1,10 @@
-// kernels_fs.hip — branch statistics of the fx-shaped branches (every width <= 4,
-// m_b <= 512) for SEVERAL parameter sets at once: per (model slot, branch) the rss of
-// the branch output against one target vector (rs-bann branch-r2, net.rs:648-656) and
-// the column sums of the effect-size chain's first-layer deltas, from which the
-// population effect sizes follow (rs-bann population-effect-sizes, net.rs:529-543).
-//
-// Stream and forward.  k_stats_fe is k_forward_fe (kernels_fe.hip) up to the branch
-// output: the same work items and tile ownership of the four waves, the same two-slot
-// LDS ring two tiles ahead with the padding rows unstreamed, the chunk's cumulative
-// fragments formed once for every model of the pass, the same exact int32 digit sums,
-// digit combine, scale, lane transpose and fmaf order of the head.  `out` of (model,
-// branch, individual) is bitwise the row element k_forward_fx writes.  No row leaves
-// the kernel.
+// kernels_fs.hip — branch statistics of the fx-shaped branches for SEVERAL parameter sets
+// at once: per (model slot, branch) the rss of the branch output against one target
+// vector (rs-bann branch-r2, net.rs:648-656) and the column sums of the effect-size
+// chain's first-layer deltas, from which the population effect sizes follow (rs-bann
+// population-effect-sizes, net.rs:529-543).  The pass up to the branch output (stream,
+// chunk walk, head, bits and registers) is fe_stream.h's, shared with k_forward_fe; no
+// row leaves the kernel.  This kernel's own part:
 //
 // Per model and tile, one individual per lane, after the head:
 //   rss      e = out - y_i, e^2
@@ -37,68 +31,16 @@
 // every instantiation and the variant not kept: DESIGN.md 4.8.
 #include <stdlib.h>
 
-#include "activations.h"
-#include "bann_internal.h"
-#include "fe_util.h"
+#include "fe_stream.h"
 
-#define FS_WAVES 4
-#define FS_SLOT 8192  // one tile image at <= 8 chunks
-#define FS_KM BANN_FS_KM
-#define FS_NV 5       // rss, s_0 .. s_3
+#define FS_NV 5  // rss, s_0 .. s_3
 
-// all but the youngest k (0 .. 9) vector-memory operations of this wave are complete
-__device__ __forceinline__ void fs_vm_wait(int k) {
-  switch (k) {
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-
-// the head of one model's tile with every layer kept, then the effect-size chain down to
-// delta0; the forward is fe_head's (kernels_fe.hip) expression by expression.  hw = the
-// model's [layer][20] LDS block (W_l[j][k] at 4 j + k for l >= 1, biases at 16 + k: c0 for
-// l = 0); widths below 4 are zero-padded, so padded units carry exact zeros both ways
+// the head of one model's tile (fe_head), then the effect-size chain on its kept layers down to delta0
 template <int NL, int ACT>
 __device__ __forceinline__ float fs_head(v4i (&facc)[4], float zscale, const float (*hw)[20], float (&d0)[4]) {
   constexpr int NH = NL - 1;
-  facc[3] -= facc[2];
-  facc[2] -= facc[1];
-  facc[1] -= facc[0];
-  float z0 = zscale * fe_comb4(facc[0]), z1 = (0.25f * zscale) * fe_comb4(facc[1]);
-  float z2 = (0.0625f * zscale) * fe_comb4(facc[2]), z3 = (0.015625f * zscale) * fe_comb4(facc[3]);
-  fe_swap32(z0, z2);
-  fe_swap32(z1, z3);
-  fe_swap16(z0, z1);
-  fe_swap16(z2, z3);
   float z[NH][4], a[NH][4];
-  z[0][0] = z0 + hw[0][16];
-  z[0][1] = z1 + hw[0][17];
-  z[0][2] = z2 + hw[0][18];
-  z[0][3] = z3 + hw[0][19];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a[0][k] = act_h_t<ACT>(z[0][k]);
-#pragma unroll
-  for (int l = 1; l < NH; ++l) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float s = hw[l][16 + k];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s = fmaf(a[l - 1][j], hw[l][4 * j + k], s);
-      z[l][k] = s;
-      a[l][k] = act_h_t<ACT>(s);
-    }
-  }
-  float out = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) out = fmaf(a[NH - 1][j], hw[NL - 1][4 * j], out);
+  const float out = fe_head<NL, ACT>(facc, zscale, hw, z, a);
   float err[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) err[k] = out * hw[NL - 1][4 * k];
@@ -126,17 +68,15 @@ __device__ __forceinline__ float fs_head(v4i (&facc)[4], float zscale, const flo
 // per-chunk guards, as k_forward_fe).  part: the pass's records, model j's at
 // part + j model_stride, item i's five doubles at 5 i.  y = null: no rss (record entry 0)
 template <int NL, int ACT>
-__global__ void __launch_bounds__(64 * FS_WAVES, 2)
+__global__ void __launch_bounds__(64 * FE_WAVES, 2)
     k_stats_fe(DevState st, FsModels mm, const GradItem* __restrict__ items, const float* __restrict__ y,
                double* __restrict__ part, int64_t model_stride) {
-  constexpr int NH = NL - 1;
-  constexpr int NW = FS_WAVES;
-  constexpr int NS = 2;  // tile slots per wave: the stream runs NS tiles ahead
-  __shared__ __attribute__((aligned(16))) char s_x[NW][NS][FS_SLOT];
+  constexpr int KM = BANN_FS_KM, NW = FE_WAVES, NS = FE_NS;
+  __shared__ __attribute__((aligned(16))) char s_x[NW][NS][FE_SLOT];
   __shared__ __attribute__((aligned(16))) float s_y[NW][NS][64];  // the tile's targets, individual 64 t + index
-  __shared__ __attribute__((aligned(16))) float s_hw[FS_KM][NL][20];
-  __shared__ __attribute__((aligned(16))) v4i s_rs[FS_KM][64];  // 64 x the digit row sums: the raw-byte accumulator's start
-  __shared__ double s_red[NW][FS_KM][FS_NV];
+  __shared__ __attribute__((aligned(16))) float s_hw[KM][NL][20];
+  __shared__ __attribute__((aligned(16))) v4i s_rs[KM][64];
+  __shared__ double s_red[NW][KM][FS_NV];
 
   const GradItem it = items[blockIdx.x];
   const int b = it.branch;
@@ -148,14 +88,13 @@ __global__ void __launch_bounds__(64 * FS_WAVES, 2)
   const int64_t n = st.n;
   const bool has_y = y != nullptr;
   const int tb = it.frag_begin >> 2, te = (it.frag_end + 3) >> 2;
-  const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 1, tp = lane & 1;
 
-  // per model: head parameters -> LDS, W0 digit operands, their row sums and the lane's column scale ->
-  // registers; the unused models of a short pass carry model 0's pointers (launch_stats_fe)
-  v4i A[FS_KM][8];
-  float zscale[FS_KM];
+  // per model: head parameters and 64 x the digit row sums -> LDS, W0 digit operands and the lane's column
+  // scale -> registers.  The same text as k_forward_fe (kernels_fe.hip): why not a function, fe_stream.h
+  v4i A[KM][8];
+  float zscale[KM];
 #pragma unroll
-  for (int k = 0; k < FS_KM; ++k) {
+  for (int k = 0; k < KM; ++k) {
     if (threadIdx.x < NL * 20) {
       const int l = threadIdx.x / 20, r = threadIdx.x - l * 20;
       const float* th = mm.theta[k] + bd.p_off;
@@ -166,37 +105,35 @@ __global__ void __launch_bounds__(64 * FS_WAVES, 2)
       } else {
         const int kk = r - 16;
         if (l == 0 && kk < bd.widths[0]) v = mm.fc[k][b].c0[kk];
-        if (l >= 1 && l < NH && kk < bd.widths[l]) v = th[bd.boff[l] + kk];
+        if (l >= 1 && l < NL - 1 && kk < bd.widths[l]) v = th[bd.boff[l] + kk];
       }
       s_hw[k][l][r] = v;
     }
-    zscale[k] = mm.fc[k][b].scale[g];
+    zscale[k] = mm.fc[k][b].scale[lane >> 4];
     v4i rowsum64 = v4i{0, 0, 0, 0};
     const uint8_t* dg = mm.dig[k] + bd.dig_off + lane * 16;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int cc = c < nch ? c : nch - 1;  // a chunk of the branch's image; chunks past nch: zero operands
-      const v4i a = *reinterpret_cast<const v4i*>(dg + (int64_t)cc * 1024);
-      A[k][c] = c < nch ? a : v4i{0, 0, 0, 0};
-    }
+    for (int c = 0; c < 8; ++c) A[k][c] = fe_digit_operand(dg, c, nch);
 #pragma unroll
-    for (int c = 0; c < 8; ++c) rowsum64 = fe_rowsum64_acc(A[k][c], rowsum64);
+    for (int c = 0; c < 8; ++c) rowsum64 = rowsum64_acc(A[k][c], rowsum64);
     if (wave == 0) s_rs[k][lane] = rowsum64;  // the same in every wave
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // the head parameters are in LDS before any LDS-DMA is in flight
 
+  // lane geometry, the same text as k_forward_fe (kernels_fe.hip)
+  const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 1, tp = lane & 1;
   const int gsw = g & 1;
   const uint32_t fo0 = (uint32_t)((16 * g + tq + 8 * gsw) * 16 + 8 * (tp ^ gsw));
   const uint32_t fo1 = (uint32_t)((16 * g + tq + 8 * (1 ^ gsw)) * 16 + 8 * (tp ^ 1 ^ gsw));
   const int iota = 4 * i16 + g;
-  const char* xsrc = reinterpret_cast<const char*>(st.xu2) + bd.x_off;  // wave-uniform; the lane adds 16 lane
+  const char* xsrc = reinterpret_cast<const char*>(st.xu2) + bd.x_off;
   const uint32_t xlane = (uint32_t)lane * 16u;
   const int64_t tile_bytes = (int64_t)nch * 1024;
   // the last chunk's padding rows are not streamed (as in k_forward_fx): their digit operands are zero
   const bool pad_row = 64 * (nch - 1) + 16 * (lane >> 4) + (((lane & 15) - 8 * ((lane >> 4) & 1)) & 15) >= bd.m;
   const int pieces = nch + (has_y ? 1 : 0);  // vector-memory instructions per tile
-  auto issue_tile = [&](int tt, int sl) {
+  auto issue_tile = [&](int tt, int sl) {  // the same loop as k_forward_fe's (kernels_fe.hip); why not a function: fe_stream.h
     for (int c = 0; c < nch; ++c) {
       if (c == nch - 1 && pad_row) continue;
       glds16_s(xsrc + (int64_t)tt * tile_bytes + c * 1024, xlane, &s_x[wave][sl][c * 1024]);
@@ -207,9 +144,9 @@ __global__ void __launch_bounds__(64 * FS_WAVES, 2)
     }
   };
 
-  double acc[FS_KM][FS_NV];
+  double acc[KM][FS_NV];
 #pragma unroll
-  for (int k = 0; k < FS_KM; ++k)
+  for (int k = 0; k < KM; ++k)
 #pragma unroll
     for (int c = 0; c < FS_NV; ++c) acc[k][c] = 0.0;
 
@@ -218,13 +155,15 @@ __global__ void __launch_bounds__(64 * FS_WAVES, 2)
     if (tt + j * NW < te) issue_tile(tt + j * NW, j);
   for (; tt < te; tt += NW, sl ^= 1) {
     // younger than this tile's pieces: the next tile's, nothing else (no stores, no other loads)
-    fs_vm_wait(tt + NW < te ? pieces : 0);
-    const char* xs = &s_x[wave][sl][0];
-    const float yv = has_y ? s_y[wave][sl][iota] : 0.f;
+    fe_vm_wait<9>(tt + NW < te ? pieces : 0);
+    const float yv = has_y ? s_y[wave][sl][iota] : 0.f;  // read before the refill
     const bool live = 64 * (int64_t)tt + iota < n;  // rows past n contribute to no sum
-    v4i facc[FS_KM][4];
+    // the chunk walk, the same text as k_forward_fe (kernels_fe.hip): the chunk's fragments once, then every model's
+    // MFMAs against them; the next chunk's LDS read is in flight meanwhile
+    const char* xs = &s_x[wave][sl][0];
+    v4i facc[KM][4];
 #pragma unroll
-    for (int k = 0; k < FS_KM; ++k) {
+    for (int k = 0; k < KM; ++k) {
       facc[k][0] = facc[k][1] = facc[k][2] = v4i{0, 0, 0, 0};
       facc[k][3] = s_rs[k][lane];
     }
@@ -236,21 +175,15 @@ __global__ void __launch_bounds__(64 * FS_WAVES, 2)
       if (c + 1 < 8 && c + 1 < nch) Xn = (v4u)lds_tr8_pair(xs + (c + 1) * 1024 + fo0, xs + (c + 1) * 1024 + fo1);
       const v4i f0 = (v4i)(X & 0x03030303u), f1 = (v4i)(X & 0x0F0F0F0Fu), f2 = (v4i)(X & 0x3F3F3F3Fu), f3 = (v4i)X;
 #pragma unroll
-      for (int k = 0; k < FS_KM; ++k) {
-        if (k < nk) {  // wave-uniform
-          facc[k][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[k][c], f0, facc[k][0], 0, 0, 0);
-          facc[k][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[k][c], f1, facc[k][1], 0, 0, 0);
-          facc[k][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[k][c], f2, facc[k][2], 0, 0, 0);
-          facc[k][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[k][c], f3, facc[k][3], 0, 0, 0);
-        }
+      for (int k = 0; k < KM; ++k) {
+        if (k < nk) fe_mfma4(A[k][c], f0, f1, f2, f3, facc[k]);  // wave-uniform
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    // every read of this slot (the targets included) has returned: refill it
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every read of this slot has returned: refill it
     if (tt + NS * NW < te) issue_tile(tt + NS * NW, sl);
 #pragma unroll
-    for (int k = 0; k < FS_KM; ++k) {
+    for (int k = 0; k < KM; ++k) {
       if (k < nk) {
         float d0[4];
         const float out = fs_head<NL, ACT>(facc[k], zscale[k], s_hw[k], d0);
@@ -266,7 +199,7 @@ __global__ void __launch_bounds__(64 * FS_WAVES, 2)
 
   // lanes by a fixed butterfly, waves in wave order, one record per model
 #pragma unroll
-  for (int k = 0; k < FS_KM; ++k)
+  for (int k = 0; k < KM; ++k)
 #pragma unroll
     for (int c = 0; c < FS_NV; ++c) {
       const double v = wave_sum_d(acc[k][c]);
@@ -282,35 +215,16 @@ __global__ void __launch_bounds__(64 * FS_WAVES, 2)
   }
 }
 
-template <int NL>
-static void launch_fs_nl(const DevState& st, const FsModels& mm, const GradItem* items, int32_t nitems, int act,
-                         const float* y, double* part, int64_t model_stride, hipStream_t s) {
-  const dim3 grid((unsigned)nitems), block(64 * FS_WAVES);
-  switch (act) {
-    case 0: hipLaunchKernelGGL((k_stats_fe<NL, 0>), grid, block, 0, s, st, mm, items, y, part, model_stride); break;
-    case 1: hipLaunchKernelGGL((k_stats_fe<NL, 1>), grid, block, 0, s, st, mm, items, y, part, model_stride); break;
-    case 2: hipLaunchKernelGGL((k_stats_fe<NL, 2>), grid, block, 0, s, st, mm, items, y, part, model_stride); break;
-    case 3: hipLaunchKernelGGL((k_stats_fe<NL, 3>), grid, block, 0, s, st, mm, items, y, part, model_stride); break;
-    default: hipLaunchKernelGGL((k_stats_fe<NL, 4>), grid, block, 0, s, st, mm, items, y, part, model_stride); break;
-  }
-}
-
 // items: one fx launch group
 void launch_stats_fe(const DevState& st, const FsModels& mm, const GradItem* items, int32_t nitems, int32_t L,
                      int32_t act, const float* y, double* part, int64_t model_stride, hipStream_t s) {
   if (nitems <= 0 || mm.nk <= 0) return;
-  FsModels mf = mm;  // unused models: model 0's pointers (the kernel's prologue reads every model)
-  for (int k = mm.nk; k < BANN_FS_KM; ++k) {
-    mf.theta[k] = mm.theta[0];
-    mf.dig[k] = mm.dig[0];
-    mf.fc[k] = mm.fc[0];
-  }
-  switch (L) {
-    case 2: launch_fs_nl<2>(st, mf, items, nitems, act, y, part, model_stride, s); break;
-    case 3: launch_fs_nl<3>(st, mf, items, nitems, act, y, part, model_stride, s); break;
-    case 4: launch_fs_nl<4>(st, mf, items, nitems, act, y, part, model_stride, s); break;
-    default: break;
-  }
+  FsModels mf = mm;
+  mf.fill_unused();
+  fe_dispatch(L, act, [&](auto nl, auto a) {
+    hipLaunchKernelGGL((k_stats_fe<decltype(nl)::value, decltype(a)::value>), dim3((unsigned)nitems),
+                       dim3(64 * FE_WAVES), 0, s, st, mf, items, y, part, model_stride);
+  });
 }
 
 // ---------------------------------------------------------------------------

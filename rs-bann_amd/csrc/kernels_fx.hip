@@ -44,8 +44,8 @@
 #include "../../include/bann.h"
 #include "activations.h"
 #include "bann_internal.h"
+#include "fe_util.h"
 #include "fx_shapes.h"
-#include "kernel_util.h"
 #include "update_core.h"
 
 #define FX_WAVES 4        // waves per workgroup (one work item, tiles interleaved)
@@ -64,7 +64,7 @@
 // the 2-bit field holds -1 .. 1).  The forward takes CUMULATIVE fragments -- x & 0x03, x & 0x0F,
 // x & 0x3F and the raw byte: 3 ANDs per dword instead of 5 -- and recovers the in-place fields
 // exactly in int32 once per tile: F1 = C1 - C0, F2 = C2 - C1, F3 = C3 - C2 with C3 started at
-// 64 sum_k A (the W0-digit row sums over the wave's chunks, fx_rowsum64), so F_q = 4^q S_q as
+// 64 sum_k A (the W0-digit row sums over the wave's chunks, rowsum64_acc), so F_q = 4^q S_q as
 // before and z keeps its bits.  The backward keeps field 3 in place too (x & 0xC0 = 64 (f3 - 1):
 // one AND instead of a shift and an AND), with the delta0 digits of K-group 3 pre-divided by 64;
 // the -1 comes back as 64 sum_(i in group 3) digit_i, one MFMA per tile against FX_ONES3, added
@@ -138,8 +138,6 @@
 // has a whole tile more to land than when it is issued in the forward (the
 // one-tile-ahead and burst variants measured slower: DESIGN.md 4)
 
-typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-
 #define FX_ONES3 (v4i{0, 0, 0, 0x40404040})  // 64 in every K slot of field 3 (the backward's group 3)
 
 // one chunk of the forward: the four cumulative fragments of a quad-byte operand
@@ -149,24 +147,16 @@ __device__ __forceinline__ void fx_fwd_chunk(v4i A, v4u X, v4i (&facc)[4]) {
   facc[2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, (v4i)(X & 0x3F3F3F3Fu), facc[2], 0, 0, 0);
   facc[3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, (v4i)X, facc[3], 0, 0, 0);
 }
-// cumulative sums -> in-place fields F_q = 4^q S_q (facc[3] started at fx_rowsum64)
+// cumulative sums -> in-place fields F_q = 4^q S_q (facc[3] started at the rowsum64_acc sum)
 __device__ __forceinline__ void fx_fwd_fields(v4i (&facc)[4]) {
   facc[3] -= facc[2];
   facc[2] -= facc[1];
   facc[1] -= facc[0];
 }
-// 64 sum_k A[.][k] for the digit operands of chunks [0, nc): facc[3]'s start
-__device__ __forceinline__ v4i fx_rowsum64_acc(v4i A, v4i acc) {
-  return __builtin_amdgcn_mfma_i32_16x16x64_i8(A, v4i{0x40404040, 0x40404040, 0x40404040, 0x40404040}, acc, 0, 0, 0);
-}
 // the backward's fragments of one window dword: every field in place (x 1, 4, 16, and
 // 64 (f3 - 1)); the delta0 digits of K-group p carry 4^-p (p = 3: 64^-1)
 __device__ __forceinline__ v4i fx_bwd_unpack(uint32_t wv) {
   return v4i{(int)(wv & 0x03030303u), (int)(wv & 0x0C0C0C0Cu), (int)(wv & 0x30303030u), (int)(wv & 0xC0C0C0C0u)};
-}
-
-__device__ __forceinline__ float ufl(float v) {  // make a wave-uniform value scalar
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 
 // all but the youngest k vector-memory operations of this wave are complete
@@ -182,14 +172,6 @@ __device__ __forceinline__ void vm_wait(int k) {
     case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
-}
-
-__device__ __forceinline__ float sgpr_f(float v) {  // a wave-uniform value, pinned to a scalar register
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
-__device__ __forceinline__ float comb4(v4i d) {  // sum_d D_d 2^(-7 d)
-  return (float)d[0] + (float)d[1] * 0x1p-7f + (float)d[2] * 0x1p-14f + (float)d[3] * 0x1p-21f;
 }
 
 // delta0 digits: V = rint(x 2^e), |V| < 2^27, as four signed 8-bit digits
@@ -222,19 +204,6 @@ __device__ __forceinline__ v4i shr_digits(v4i G, int sh) {
   const int64_t N = (int64_t)G[0] + ((int64_t)G[1] << 8) + ((int64_t)G[2] << 16) + ((int64_t)G[3] << 24);
   const int64_t M = N >> (sh < 63 ? sh : 63);
   return v4i{(int)(M & 255), (int)((M >> 8) & 255), (int)((M >> 16) & 255), (int)(M >> 24)};
-}
-
-__device__ __forceinline__ void swap32(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                                  false, false);
-  a = __builtin_bit_cast(float, (unsigned)r[0]);
-  b = __builtin_bit_cast(float, (unsigned)r[1]);
-}
-__device__ __forceinline__ void swap16(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                                  false, false);
-  a = __builtin_bit_cast(float, (unsigned)r[0]);
-  b = __builtin_bit_cast(float, (unsigned)r[1]);
 }
 
 // NCH: 8 = every branch of the launch has exactly 8 chunks (no per-chunk guards,
@@ -382,7 +351,7 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
   asm volatile("" : "+v"(zscale));
   __syncthreads();
   v4i rowsum64 = v4i{0, 0, 0, 0};  // the forward's facc[3] start (field 3 stored as code - 1)
-  for (int c = 0; c < nch; ++c) rowsum64 = fx_rowsum64_acc(*reinterpret_cast<const v4i*>(&s_w0[c * 1024 + lane * 16]), rowsum64);
+  for (int c = 0; c < nch; ++c) rowsum64 = rowsum64_acc(*reinterpret_cast<const v4i*>(&s_w0[c * 1024 + lane * 16]), rowsum64);
   // head weights as wave-uniform values: scalar registers for the whole item (the
   // per-tile LDS broadcasts serialised the head on their latencies)
   float uW[NL][4][4], uB[NH][4];
@@ -1024,9 +993,9 @@ __global__ void __launch_bounds__(64 * FX_WAVES, 2)
   v4i rowsum64 = v4i{0, 0, 0, 0};  // facc[3]'s start (field 3 stored as code - 1)
   if constexpr (NU > 0) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) rowsum64 = fx_rowsum64_acc(Areg[c], rowsum64);
+    for (int c = 0; c < 8; ++c) rowsum64 = rowsum64_acc(Areg[c], rowsum64);
   } else {
-    for (int c = 0; c < nch; ++c) rowsum64 = fx_rowsum64_acc(*reinterpret_cast<const v4i*>(&s_w0[c * 1024 + lane * 16]), rowsum64);
+    for (int c = 0; c < nch; ++c) rowsum64 = rowsum64_acc(*reinterpret_cast<const v4i*>(&s_w0[c * 1024 + lane * 16]), rowsum64);
   }
   float uWm[NL][4][4], uB[NH][4];  // head weights W_l[j][k] (l >= 1; output layer: k = 0) and biases, scalar
 #pragma unroll
@@ -1308,7 +1277,7 @@ __global__ void __launch_bounds__(64 * 8, 1)
     asm volatile("" : "+v"(zscale));
     v4i rowsum64 = v4i{0, 0, 0, 0};
 #pragma unroll
-    for (int c = 0; c < 8; ++c) rowsum64 = fx_rowsum64_acc(Areg[c], rowsum64);
+    for (int c = 0; c < 8; ++c) rowsum64 = rowsum64_acc(Areg[c], rowsum64);
     float uWm[NL][4][4], uB[NH][4];
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
@@ -1634,9 +1603,9 @@ __global__ void __launch_bounds__(64 * FXL_MAXW, 1)
     if constexpr (RES) {
 #pragma unroll
       for (int c = 0; c < CPW; ++c)
-        if (FULL || c < cw) rs = fx_rowsum64_acc(Dres[c], rs);
+        if (FULL || c < cw) rs = rowsum64_acc(Dres[c], rs);
     } else {
-      for (int c = 0; c < cw; ++c) rs = fx_rowsum64_acc(*reinterpret_cast<const v4i*>(dsrc + c * 1024), rs);
+      for (int c = 0; c < cw; ++c) rs = rowsum64_acc(*reinterpret_cast<const v4i*>(dsrc + c * 1024), rs);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     zrow = (0.015625f * zscale) * comb4(rs);
@@ -2308,7 +2277,7 @@ __global__ void __launch_bounds__(64 * (FXH_MAXC + 1), 1)
     asm volatile("" : "+v"(zscale));
     v4i rowsum64 = v4i{0, 0, 0, 0};  // facc[3]'s start (field 3 stored as code - 1)
 #pragma unroll
-    for (int c = 0; c < CW; ++c) rowsum64 = fx_rowsum64_acc(Dres[c], rowsum64);
+    for (int c = 0; c < CW; ++c) rowsum64 = rowsum64_acc(Dres[c], rowsum64);
     for (int k = 0; k < NSL && k < T; ++k) issue_tile(k);  // every slot filled; tile k + NSL refills slot k in B(k)
     v4i acc[NWC];
 #pragma unroll
