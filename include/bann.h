@@ -113,11 +113,28 @@ int bann_genotypes_download(bann_ctx* ctx, const int32_t* snp_idx, int32_t m, in
  * in bounded blocks */
 int bann_genotypes_load_bed(bann_ctx* ctx, const char* stem);
 
+/* Opt-in record of which calls are present (default keep = 0).  The genotype image stores a missing
+ * .bed code (01) as 0 and cannot tell it from a homozygous call.  With keep != 0,
+ * bann_genotypes_upload_bed and bann_genotypes_load_bed fill a second image of the cohort image's
+ * exact layout beside it, the presence image: row = marker, rowb bytes, field 2p of byte q is 1 iff
+ * individual 4q+p < n and its .bed code is not 01, else 0 (the .bed's padding codes and the row
+ * padding are 0: absent).  The genotype image and everything computed from it (training, prediction,
+ * bann_genotypes_download, ld_band, ld_graph) are byte-identical with keep on or off.
+ * bann_genotypes_upload (int8) and bann_genotypes_synthetic have no missing calls: everyone is present.
+ * Memory: +100 % of the cohort image, only while keep is on, the raw image is resident
+ * (bann_finalize(free_raw != 0) frees both) and the cohort has a missing call at all: a cohort
+ * without one keeps no presence image.  Call it before genotypes are loaded: BANN_E_STATE afterwards. */
+int bann_genotypes_keep_missing(bann_ctx* ctx, int32_t keep);
+/* out[j - first] = number of missing calls of marker j, j in [first, first+count).  BANN_E_STATE with
+ * keep off or when the cohort image is gone; BANN_E_ARG for a range outside the cohort. */
+int bann_genotypes_missing_counts(bann_ctx* ctx, int64_t first, int64_t count, int32_t* out);
+
 /* ---------------- LD between markers, from the resident cohort ----------------
  * Replaces the PLINK --r2 run whose table CorrGraph::from_plink_ld (group/centered.rs:54-89) reads:
  * the reference's group-by-ld does not compute LD itself.  For markers j < k <= j + window, with the
  * genotype values g in {0,1,2} exactly as the image stores them (a missing .bed code is 0,
- * bed_lookup_tables.rs:4; PLINK leaves missing pairs out of its sums, this does not):
+ * bed_lookup_tables.rs:4; PLINK leaves missing pairs out of its sums, this does not: the pairwise
+ * calls below do):
  *   s_j = sum g_ij, q_j = sum g_ij^2, S_jk = sum g_ij g_ik                    exact int32
  *   cov = n S_jk - s_j s_k, v_j = n q_j - s_j^2                               exact int64
  *   r2  = ((double)cov * (double)cov) / ((double)v_j * (double)v_k)           f64, in this order
@@ -142,12 +159,42 @@ int bann_genotypes_ld_graph(bann_ctx* ctx, int32_t window, float r2_min, const i
                             int64_t max_bp, int64_t* num_edges);
 /* CSR of the kept graph: offsets[M+1], neighbours[2*num_edges], each list ascending */
 int bann_genotypes_ld_graph_get(bann_ctx* ctx, int64_t* offsets, int32_t* neighbours);
-/* bytes of the S band of one marker block of the calls above (default and maximum 128 MiB;
- * bytes <= 0 restores the default): a smaller limit means more, smaller blocks on a device that
- * is short of memory.  Band and graph do not depend on it. */
+/* bytes of the S band of one marker block of the calls above, and of the six bands together of one
+ * marker block of the pairwise calls below (default and maximum 128 MiB; bytes <= 0 restores the
+ * default): a smaller limit means more, smaller blocks on a device that is short of memory.  Band
+ * and graph do not depend on it. */
 int bann_genotypes_ld_scratch_limit(bann_ctx* ctx, int64_t bytes);
-/* HIP-event milliseconds of the device kernels of the last ld_band / ld_graph call */
+/* HIP-event milliseconds of the device kernels of the last ld_band / ld_graph call, pairwise or not */
 int bann_genotypes_ld_timing(const bann_ctx* ctx, double* kernel_ms);
+
+/* ---------------- pairwise-complete LD: a pair's missing individuals left out, as PLINK does --------
+ * Needs bann_genotypes_keep_missing(ctx, 1) before the load: BANN_E_STATE otherwise.  For markers
+ * j < k <= j + window, with g the image's genotype (0 where missing, so g m = g) and m the presence
+ * bit, all sums over the individuals:
+ *   N  = sum m_j m_k      a  = sum g_j m_k      b  = sum m_j g_k
+ *   qa = sum g_j^2 m_k    qb = sum m_j g_k^2    S  = sum g_j g_k                 exact int32
+ *   cov = N S - a b       v_a = N qa - a^2      v_b = N qb - b^2                 exact int64
+ *   r2  = ((double)cov * (double)cov) / ((double)v_a * (double)v_b)              f64, in this order
+ * and r2 = 0 if v_a == 0 or v_b == 0: that covers N == 0 and a marker that is constant among this
+ * pair's jointly present individuals even though it varies over the whole cohort.  The band holds
+ * (float)r2; an edge is r2 >= (double)r2_min on the f64 value; n <= 536870911 as above.  S is the S
+ * band of the calls above; the other five sums are five more banded products of the same kernel
+ * shape, so a pairwise call costs about six plain ones.  Without a missing call in the cohort the
+ * sums are N = n, a = s_j, b = s_k, qa = q_j, qb = q_k and the results are those of ld_band /
+ * ld_graph, bit for bit.  The six int32 bands of one marker block together stay inside the scratch
+ * limit: block rows = limit / (6 * 4 * window) rounded down to whole 128-marker tiles, BANN_E_ARG
+ * when 128 rows of six bands exceed the limit (at the default 128 MiB: a window above 43690 after
+ * clipping to num_markers - 1).  Every other argument and state error is that of ld_band / ld_graph.
+ * Results do not depend on how the device work is cut. */
+
+/* r2_out as bann_genotypes_ld_band; npairs_out (nullable) has r2_out's layout and holds N, 0 where
+ * j+d >= num_markers.  A caller who wants a minimum number of pairs per edge filters on it. */
+int bann_genotypes_ld_band_pairwise(bann_ctx* ctx, int32_t window, int64_t first, int64_t count, float* r2_out,
+                                    int32_t* npairs_out);
+/* bann_genotypes_ld_graph on the pairwise-complete r2; the graph replaces the kept one and is read
+ * with bann_genotypes_ld_graph_get */
+int bann_genotypes_ld_graph_pairwise(bann_ctx* ctx, int32_t window, float r2_min, const int32_t* chrom,
+                                     const int64_t* bp, int64_t max_bp, int64_t* num_edges);
 
 /* ---------------- files on either side of the path (host only, no device) ---------------- */
 /* BedDims (io/dims.rs:15-34): stem.dims "n M", else the .fam / .bim line counts */

@@ -107,6 +107,12 @@ SIGNATURES = {
     "bann_genotypes_ld_graph_get": (C.c_int, [_P, C.POINTER(_i64), _pi32]),
     "bann_genotypes_ld_timing": (C.c_int, [_P, _pf64]),
     "bann_genotypes_ld_scratch_limit": (C.c_int, [_P, _i64]),
+    # the presence image and the pairwise-complete LD (a pair's missing individuals left out)
+    "bann_genotypes_keep_missing": (C.c_int, [_P, _i32]),
+    "bann_genotypes_missing_counts": (C.c_int, [_P, _i64, _i64, _pi32]),
+    "bann_genotypes_ld_band_pairwise": (C.c_int, [_P, _i32, _i64, _i64, _pf32, _pi32]),
+    "bann_genotypes_ld_graph_pairwise": (C.c_int, [_P, _i32, _f32, _pi32, C.POINTER(_i64), _i64,
+                                                   C.POINTER(_i64)]),
     "bann_io_last_error": (C.c_char_p, []),
     "bann_bim_read": (C.c_int, [C.c_char_p, C.POINTER(_i64), _pi32, C.POINTER(_i64)]),
     "bann_ld_graph_read_plink": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_i64), C.POINTER(_i64),

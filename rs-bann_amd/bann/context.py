@@ -101,6 +101,20 @@ class BannContext:
         s = _f32(sigma)
         self._check(self._lib.bann_genotypes_set_stats(self._h, _ptr(m, C.c_float), _ptr(s, C.c_float)))
 
+    def keep_missing(self, on: bool = True):
+        """keep a record of which .bed calls are present (the presence image, include/bann.h) for
+        missing_counts and the pairwise LD calls; before the genotypes are loaded.  Costs the cohort
+        image's memory once more while the raw image is resident and the cohort has a missing call."""
+        self._check(self._lib.bann_genotypes_keep_missing(self._h, 1 if on else 0))
+
+    def missing_counts(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """int32 [count]: missing calls of markers first .. first + count (needs keep_missing)."""
+        if count is None:
+            count = self.num_markers - first
+        out = np.zeros(max(int(count), 0), np.int32)
+        self._check(self._lib.bann_genotypes_missing_counts(self._h, int(first), int(count), _ptr(out, C.c_int32)))
+        return out
+
     def download_genotypes(self, snp_idx: Sequence[int]) -> np.ndarray:
         idx = np.ascontiguousarray(snp_idx, dtype=np.int32)
         out = np.zeros((idx.size, self.n), np.int8)
@@ -108,19 +122,33 @@ class BannContext:
         return out
 
     # ------------------------------------------------------------------- LD
-    def ld_band(self, window: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+    def ld_band(self, window: int, first: int = 0, count: Optional[int] = None, pairwise: bool = False,
+                return_pairs: bool = False):
         """(count, window) f32: row j - first, column d - 1 = r2 of markers j and j + d of the resident
-        cohort (0 where j + d >= num_markers); exact integer sums, one f64 division (include/bann.h)."""
+        cohort (0 where j + d >= num_markers); exact integer sums, one f64 division (include/bann.h).
+        pairwise: r2 over each pair's jointly present individuals, as PLINK (needs keep_missing); a
+        missing call counts as genotype 0 otherwise.  return_pairs (pairwise only): (r2, N), N the int32
+        number of jointly present individuals in the band's layout."""
+        if return_pairs and not pairwise:
+            raise ValueError("return_pairs needs pairwise=True")
         if count is None:
             count = self.num_markers - first
         out = np.zeros((max(int(count), 0), max(int(window), 0)), np.float32)
-        self._check(self._lib.bann_genotypes_ld_band(self._h, int(window), int(first), int(count),
-                                                     _ptr(out, C.c_float)))
-        return out
+        if not pairwise:
+            self._check(self._lib.bann_genotypes_ld_band(self._h, int(window), int(first), int(count),
+                                                         _ptr(out, C.c_float)))
+            return out
+        pairs = np.zeros(out.shape, np.int32) if return_pairs else None
+        self._check(self._lib.bann_genotypes_ld_band_pairwise(self._h, int(window), int(first), int(count),
+                                                              _ptr(out, C.c_float),
+                                                              _ptr(pairs, C.c_int32) if return_pairs else None))
+        return (out, pairs) if return_pairs else out
 
-    def ld_graph(self, window: int, r2_min: float = 0.2, chrom=None, bp=None, max_bp: int = 0):
+    def ld_graph(self, window: int, r2_min: float = 0.2, chrom=None, bp=None, max_bp: int = 0,
+                 pairwise: bool = False):
         """(offsets, neighbours): symmetric CSR of the pairs 0 < k - j <= window with r2 >= r2_min, and,
-        with chrom / bp given, on one chromosome and (max_bp <= 0 or) at most max_bp apart."""
+        with chrom / bp given, on one chromosome and (max_bp <= 0 or) at most max_bp apart.  pairwise:
+        on the pairwise-complete r2 (see ld_band; needs keep_missing)."""
         if (chrom is None) != (bp is None):
             raise ValueError("chrom and bp are given together or not at all")
         pc = pb = None
@@ -131,20 +159,20 @@ class BannContext:
                 raise ValueError("chrom and bp need one entry per marker")
             pc, pb = _ptr(ca, C.c_int32), _ptr(ba, C.c_int64)
         ne = C.c_int64()
-        self._check(self._lib.bann_genotypes_ld_graph(self._h, int(window), float(r2_min), pc, pb, int(max_bp),
-                                                      C.byref(ne)))
+        fn = self._lib.bann_genotypes_ld_graph_pairwise if pairwise else self._lib.bann_genotypes_ld_graph
+        self._check(fn(self._h, int(window), float(r2_min), pc, pb, int(max_bp), C.byref(ne)))
         off = np.zeros(self.num_markers + 1, np.int64)
         nb = np.zeros(max(2 * ne.value, 1), np.int32)
         self._check(self._lib.bann_genotypes_ld_graph_get(self._h, _ptr(off, C.c_int64), _ptr(nb, C.c_int32)))
         return off, nb[:2 * ne.value]
 
     def ld_scratch_limit(self, nbytes: int = 0):
-        """bytes of the S band of one marker block of ld_band / ld_graph (0: the default, 128 MiB, also the
-        maximum); the results do not depend on it."""
+        """bytes of the S band of one marker block of ld_band / ld_graph, of the six bands together with
+        pairwise=True (0: the default, 128 MiB, also the maximum); the results do not depend on it."""
         self._check(self._lib.bann_genotypes_ld_scratch_limit(self._h, int(nbytes)))
 
     def ld_timing(self) -> float:
-        """HIP-event milliseconds of the device kernels of the last ld_band / ld_graph call."""
+        """HIP-event milliseconds of the device kernels of the last ld_band / ld_graph call, pairwise or not."""
         ms = C.c_double()
         self._check(self._lib.bann_genotypes_ld_timing(self._h, C.byref(ms)))
         return ms.value

@@ -10,6 +10,7 @@
   centered_grouping   CorrGraph::centered_grouping (group/centered.rs:91-133)
   write_grouping      MarkerGrouping::to_file (group/grouping.rs:16-31)
   group_by_ld         rs-bann group-by-ld with the LD taken from the context's cohort on the device
+  encode_bed_payload  int8 genotypes with -1 for a missing call -> the variant-major .bed payload
   list_model_files / write_predictions_csv   the model listing and the CSV records of
                       rs-bann predict (rs-bann.rs:288-311); pure Python
   write_branch_r2_csv / write_population_effect_sizes_json   the outputs of rs-bann branch-r2
@@ -123,15 +124,38 @@ def write_grouping(path: str, groups) -> None:
                                             mk.ctypes.data_as(C.POINTER(C.c_int32))), f"bann_grouping_write({path})")
 
 
-def group_by_ld(ctx, window: int, r2_min: float, min_group_size: int, bim: str = None, max_bp: int = 0):
+def group_by_ld(ctx, window: int, r2_min: float, min_group_size: int, bim: str = None, max_bp: int = 0,
+                missing: str = "zero"):
     """rs-bann group-by-ld on the context's resident cohort: the LD graph from the device (r2 >= r2_min
     within window markers; with a .bim also one chromosome and, for max_bp > 0, at most max_bp apart),
-    then the centered grouping.  Returns (groups, num_ungrouped)."""
+    then the centered grouping.  Returns (groups, num_ungrouped).
+    missing: "zero" counts a missing call as genotype 0, as the image stores it; "pairwise" leaves a
+    pair's missing individuals out of that pair's r2, as PLINK does (the context needs keep_missing()
+    before its .bed load)."""
+    if missing not in ("zero", "pairwise"):
+        raise ValueError('missing is "zero" or "pairwise"')
     chrom = bp = None
     if bim is not None:
         chrom, bp = read_bim(bim)
-    off, nb = ctx.ld_graph(window, r2_min, chrom, bp, max_bp)
+    off, nb = ctx.ld_graph(window, r2_min, chrom, bp, max_bp, pairwise=missing == "pairwise")
     return centered_grouping(off, nb, min_group_size)
+
+
+def encode_bed_payload(g) -> bytes:
+    """int8 [M][n] genotypes in {0,1,2}, -1 for a missing call -> the variant-major .bed payload
+    (no signature): ceil(n/4) bytes per marker, individual 4q+p in bits 2p of byte q, 2 -> 00, 1 -> 10,
+    0 -> 11, -1 -> 01, padding bits 0.  The inverse of the load LUT for the three called values."""
+    a = np.asarray(g)
+    if a.ndim != 2:
+        raise ValueError("genotypes are [num_markers][n]")
+    if a.size and (a.min() < -1 or a.max() > 2):
+        raise ValueError("genotypes are 0, 1, 2 or -1 (missing)")
+    M, n = a.shape
+    code = np.array([1, 3, 2, 0], np.uint8)[a.astype(np.int64) + 1]  # index -1 .. 2 -> 01, 11, 10, 00
+    padded = np.zeros((M, (n + 3) // 4 * 4), np.uint8)
+    padded[:, :n] = code
+    q = padded.reshape(M, -1, 4)
+    return (q[:, :, 0] | (q[:, :, 1] << 2) | (q[:, :, 2] << 4) | (q[:, :, 3] << 6)).astype(np.uint8).tobytes()
 
 
 def read_phen(path: str) -> np.ndarray:

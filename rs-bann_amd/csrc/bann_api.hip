@@ -576,7 +576,7 @@ extern "C" int bann_ctx_destroy(bann_ctx* ctx) {
   }
   free_plan(ctx->lf);
   models_release(ctx);
-  void* bufs[] = {ctx->d_g, ctx->d_mu, ctx->d_sigma, ctx->d_br, ctx->d_xu2, ctx->d_xi, ctx->d_dig, ctx->d_fc, ctx->d_mub,
+  void* bufs[] = {ctx->d_g, ctx->d_pm, ctx->d_mu, ctx->d_sigma, ctx->d_br, ctx->d_xu2, ctx->d_xi, ctx->d_dig, ctx->d_fc, ctx->d_mub,
                   ctx->d_sigb, ctx->d_theta, ctx->d_mom, ctx->d_eps, ctx->d_theta0, ctx->d_lam, ctx->d_lamld,
                   ctx->d_grad, ctx->d_part, ctx->d_rss_part, ctx->d_y, ctx->d_pred, ctx->d_pred0, ctx->d_scr, ctx->d_eprec,
                   ctx->d_u, ctx->d_h0, ctx->d_htrace, ctx->d_ld, ctx->d_rss, ctx->d_status, ctx->d_uturn,
@@ -625,9 +625,11 @@ int alloc_genotypes(bann_ctx* ctx, int64_t n, int64_t M) {
   if (n <= 0 || M <= 0) return fail(ctx, BANN_E_SHAPE, "n and num_markers must be positive");
   CK(hipSetDevice(ctx->device));
   dfree(ctx->d_g);
+  dfree(ctx->d_pm);
   dfree(ctx->d_mu);
   dfree(ctx->d_sigma);
-  ctx->d_g = nullptr;
+  ctx->d_g = ctx->d_pm = nullptr;
+  ctx->missing_total = 0;
   ctx->d_mu = ctx->d_sigma = nullptr;
   ctx->n = n;
   ctx->M = M;
@@ -635,6 +637,62 @@ int alloc_genotypes(bann_ctx* ctx, int64_t n, int64_t M) {
   CK(dalloc(&ctx->d_g, ctx->rowb * M));
   CK(dalloc(&ctx->d_mu, M));
   CK(dalloc(&ctx->d_sigma, M));
+  return BANN_OK;
+}
+
+int alloc_presence(bann_ctx* ctx) {
+  if (!ctx->keep_missing) return BANN_OK;
+  CK(dalloc(&ctx->d_pm, ctx->rowb * ctx->M));
+  return BANN_OK;
+}
+
+int finish_presence(bann_ctx* ctx) {
+  if (!ctx->d_pm) return BANN_OK;
+  int32_t* d_cnt = nullptr;
+  CK(dalloc(&d_cnt, ctx->M));
+  std::vector<int32_t> cnt((size_t)ctx->M);
+  launch_missing_counts(ctx->d_pm, ctx->rowb, ctx->n, 0, ctx->M, d_cnt, ctx->stream);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)ctx->M * 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  dfree(d_cnt);
+  CK(e);
+  ctx->missing_total = 0;
+  for (int32_t c : cnt) ctx->missing_total += c;
+  if (ctx->missing_total == 0) {  // everyone is present: the pairwise calls need no image for that
+    dfree(ctx->d_pm);
+    ctx->d_pm = nullptr;
+  }
+  return BANN_OK;
+}
+
+extern "C" int bann_genotypes_keep_missing(bann_ctx* ctx, int32_t keep) {
+  if (!ctx) return BANN_E_ARG;
+  if (ctx->M > 0) return fail(ctx, BANN_E_STATE, "bann_genotypes_keep_missing comes before the genotypes are loaded");
+  ctx->keep_missing = keep != 0;
+  return BANN_OK;
+}
+
+extern "C" int bann_genotypes_missing_counts(bann_ctx* ctx, int64_t first, int64_t count, int32_t* out) {
+  if (!ctx) return BANN_E_ARG;
+  if (!ctx->keep_missing) return fail(ctx, BANN_E_STATE, "missing calls are not kept (bann_genotypes_keep_missing)");
+  if (!ctx->d_g) return fail(ctx, BANN_E_STATE, "the cohort image is not resident (no genotypes loaded, or freed at bann_finalize)");
+  if (first < 0 || count < 0 || first + count > ctx->M) return fail(ctx, BANN_E_ARG, "marker range outside the cohort");
+  if (count == 0) return BANN_OK;
+  if (!out) return fail(ctx, BANN_E_ARG, "out is null");
+  if (!ctx->d_pm) {  // no missing call in the cohort
+    std::fill(out, out + count, 0);
+    return BANN_OK;
+  }
+  CK(hipSetDevice(ctx->device));
+  int32_t* d_cnt = nullptr;
+  CK(dalloc(&d_cnt, count));
+  launch_missing_counts(ctx->d_pm, ctx->rowb, ctx->n, first, count, d_cnt, ctx->stream);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_cnt, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  dfree(d_cnt);
+  CK(e);
   return BANN_OK;
 }
 
@@ -673,6 +731,7 @@ extern "C" int bann_genotypes_upload(bann_ctx* ctx, const int8_t* g, int64_t n, 
 extern "C" int bann_genotypes_upload_bed(bann_ctx* ctx, const uint8_t* payload, int64_t n, int64_t num_markers) {
   if (!ctx || !payload) return BANN_E_ARG;
   int rc = alloc_genotypes(ctx, n, num_markers);
+  if (!rc) rc = alloc_presence(ctx);
   if (rc) return rc;
   // payload rows streamed through a bounded staging block, decoded into the 2-bit image
   const int64_t bpc = (n + 3) / 4;
@@ -683,13 +742,14 @@ extern "C" int bann_genotypes_upload_bed(bann_ctx* ctx, const uint8_t* payload, 
     const int64_t m = std::min(blk, num_markers - j0);
     CK(hipMemcpyAsync(d_st, payload + j0 * bpc, (size_t)(m * bpc), hipMemcpyHostToDevice, ctx->stream));
     launch_bed_to_raw(d_st, n, m, ctx->d_g + j0 * ctx->rowb, ctx->rowb, ctx->stream);
+    if (ctx->d_pm) launch_bed_to_presence(d_st, n, m, ctx->d_pm + j0 * ctx->rowb, ctx->rowb, ctx->stream);
     CK(hipGetLastError());
   }
   launch_col_stats(ctx->d_g, ctx->rowb, ctx->d_mu, ctx->d_sigma, n, num_markers, ctx->stream);
   CK(hipGetLastError());
   CK(hipStreamSynchronize(ctx->stream));
   dfree(d_st);
-  return BANN_OK;
+  return finish_presence(ctx);
 }
 
 extern "C" int bann_genotypes_synthetic(bann_ctx* ctx, int64_t n, int64_t num_markers, uint64_t seed) {
@@ -1038,7 +1098,8 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   CK(hipStreamSynchronize(ctx->stream));
   if (free_raw) {
     dfree(ctx->d_g);
-    ctx->d_g = nullptr;
+    dfree(ctx->d_pm);
+    ctx->d_g = ctx->d_pm = nullptr;
   }
   return BANN_OK;
 }

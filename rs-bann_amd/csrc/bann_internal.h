@@ -172,6 +172,10 @@ void launch_synthetic_genotypes(uint8_t* raw, int64_t rowb, float* mu, float* si
 void launch_i8_to_raw(const int8_t* g, int64_t n, int64_t m, uint8_t* raw, int64_t rowb, int32_t* flag,
                       hipStream_t s);
 void launch_bed_to_raw(const uint8_t* payload, int64_t n, int64_t m, uint8_t* raw, int64_t rowb, hipStream_t s);
+// presence image (bann_genotypes_keep_missing): the genotype image's layout, field 1 = the call is there
+void launch_bed_to_presence(const uint8_t* payload, int64_t n, int64_t m, uint8_t* pres, int64_t rowb, hipStream_t s);
+void launch_missing_counts(const uint8_t* pres, int64_t rowb, int64_t n, int64_t j0, int64_t m, int32_t* out,
+                           hipStream_t s);
 void launch_col_stats(const uint8_t* raw, int64_t rowb, float* mu, float* sigma, int64_t n, int64_t M,
                       hipStream_t s);
 void launch_unpack_markers(const uint8_t* raw, int64_t rowb, const int32_t* snp_idx, int32_t m, int64_t n,
@@ -332,3 +336,14 @@ void launch_ld_r2(int32_t* S, int32_t rows, int32_t window, int64_t row0, int64_
 void launch_ld_mask(const int32_t* S, int32_t rows, int32_t window, int32_t words, int64_t row0, int64_t M, int64_t n,
                     int64_t stat0, const int32_t* st, const int32_t* qt, double r2_min, const int32_t* chrom,
                     const int64_t* bp, int64_t max_bp, uint32_t* mask, hipStream_t s);
+// the pairwise-complete r2 (bann.h): six int32 bands of one block, band b at bands[b * stride], each of the
+// S band's layout and zeroed by the caller.  launch_ld_band fills LD_BAND_S, launch_ld_band_pw the other
+// five from the genotype image and the presence image (same layout, field 1 = called)
+enum { LD_BAND_S = 0, LD_BAND_N = 1, LD_BAND_A = 2, LD_BAND_B = 3, LD_BAND_QA = 4, LD_BAND_QB = 5, LD_BANDS = 6 };
+void launch_ld_band_pw(const uint8_t* raw, const uint8_t* pres, int64_t rowb, int64_t M, int64_t row0, int32_t rows,
+                       int32_t window, int32_t ksplit_target, int32_t* bands, int64_t stride, hipStream_t s);
+void launch_ld_r2_pw(int32_t* bands, int64_t stride, int32_t rows, int32_t window, int64_t row0, int64_t M,
+                     hipStream_t s);
+void launch_ld_mask_pw(const int32_t* bands, int64_t stride, int32_t rows, int32_t window, int32_t words, int64_t row0,
+                       int64_t M, int64_t stat0, double r2_min, const int32_t* chrom, const int64_t* bp, int64_t max_bp,
+                       uint32_t* mask, hipStream_t s);

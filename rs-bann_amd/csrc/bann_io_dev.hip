@@ -27,6 +27,7 @@ extern "C" int bann_genotypes_load_bed(bann_ctx* ctx, const char* stem) {
     return fail(ctx, BANN_E_ARG, "sample-major .bed is not supported (bed.rs:200-202)");
   }
   int rc = alloc_genotypes(ctx, n, M);
+  if (!rc) rc = alloc_presence(ctx);
   if (rc) {
     fclose(f);
     return rc;
@@ -47,6 +48,7 @@ extern "C" int bann_genotypes_load_bed(bann_ctx* ctx, const char* stem) {
     }
     if (hipMemcpyAsync(d, h, (size_t)(m * bpc), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = BANN_E_HIP;
     launch_bed_to_raw(d, n, m, ctx->d_g + j0 * ctx->rowb, ctx->rowb, ctx->stream);
+    if (ctx->d_pm) launch_bed_to_presence(d, n, m, ctx->d_pm + j0 * ctx->rowb, ctx->rowb, ctx->stream);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, BANN_E_HIP, "bed decode");  // h is reused
   }
   fclose(f);
@@ -56,5 +58,5 @@ extern "C" int bann_genotypes_load_bed(bann_ctx* ctx, const char* stem) {
   launch_col_stats(ctx->d_g, ctx->rowb, ctx->d_mu, ctx->d_sigma, n, M, ctx->stream);
   CK(hipGetLastError());
   CK(hipStreamSynchronize(ctx->stream));
-  return BANN_OK;
+  return finish_presence(ctx);
 }

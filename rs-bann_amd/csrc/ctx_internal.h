@@ -71,6 +71,11 @@ struct bann_ctx {
   int64_t n = 0, M = 0;
   uint8_t* d_g = nullptr;  // 2-bit variant-major genotype image (kernels_data.hip), rowb bytes per marker
   int64_t rowb = 0;
+  // bann_genotypes_keep_missing: the presence image (d_g's layout, field 1 = the call is there) of a .bed
+  // load, kept while d_g is and only when the cohort has a missing call at all (missing_total > 0)
+  bool keep_missing = false;
+  uint8_t* d_pm = nullptr;
+  int64_t missing_total = 0;
   float* d_mu = nullptr;
   float* d_sigma = nullptr;
   // branches
@@ -206,8 +211,10 @@ struct bann_ctx {
   std::vector<int64_t> ld_off;
   std::vector<int32_t> ld_nb;
   bool ld_have = false;
-  int64_t ld_scratch = int64_t(128) << 20;  // bytes of the S band of one marker block (bann_genotypes_ld_scratch_limit)
-  double ld_ms = 0.0;  // HIP-event time of the device kernels of the last ld_band / ld_graph call
+  // bytes of the S band of one marker block, of the six bands together in the pairwise calls
+  // (bann_genotypes_ld_scratch_limit)
+  int64_t ld_scratch = int64_t(128) << 20;
+  double ld_ms = 0.0;  // HIP-event time of the device kernels of the last ld_band / ld_graph call, pairwise or not
   // in-trajectory launch timing (bann_set_launch_timing): HIP events around every
   // gradient and update launch of the leapfrog sessions, resolved at bann_leapfrog_end
   bool tm_on = false;
@@ -274,6 +281,10 @@ void run_update(bann_ctx* ctx, const Plan& p, int32_t mode, int32_t step);
 int ensure_htrace(bann_ctx* ctx, int32_t L);
 int alloc_genotypes(bann_ctx* ctx, int64_t n, int64_t M);   // the 2-bit genotype image of n x M
 int64_t stage_markers(int64_t bytes_per_marker, int64_t M);  // markers per ~256 MiB staging block
+// keep_missing, around a .bed load: allocate the presence image after alloc_genotypes (nothing with keep
+// off); after the last launch_bed_to_presence count the missing calls and drop the image if there is none
+int alloc_presence(bann_ctx* ctx);
+int finish_presence(bann_ctx* ctx);
 int ensure_predictions(bann_ctx* ctx, const int32_t* branches, int32_t nb);  // bann_residual.hip
 void launch_residual_sub(float* r, const float* d, int64_t n, hipStream_t s);
 void mark_predictions(bann_ctx* ctx, const Plan& p, bool current);

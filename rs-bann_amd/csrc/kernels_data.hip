@@ -159,6 +159,59 @@ void launch_bed_to_raw(const uint8_t* payload, int64_t n, int64_t m, uint8_t* ra
 }
 
 // ---------------------------------------------------------------------------
+// the presence image of the same payload rows (bann_genotypes_keep_missing): the
+// genotype image's layout, field 2p of byte q is 1 iff individual 4q + p < n and
+// its code is not 01.  The codes past n in the last byte are 00 in a .bed (a
+// called genotype 2): they are masked exactly as k_bed_to_raw masks the genotype,
+// and the row padding is 0
+// ---------------------------------------------------------------------------
+__global__ void k_bed_to_presence(const uint8_t* __restrict__ pl, int64_t n, int64_t m, uint8_t* __restrict__ pres,
+                                  int64_t rowb) {
+  const int64_t bpc = (n + 3) / 4;
+  const int64_t total = rowb * m;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t j = t / rowb, q = t - j * rowb;
+    uint32_t out = 0;
+    if (q < bpc) {
+      const uint32_t code = pl[j * bpc + q];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const uint32_t c = (code >> (2 * p)) & 3u;
+        if (4 * q + p < n) out |= (uint32_t)(c != 1u) << (2 * p);
+      }
+    }
+    pres[t] = (uint8_t)out;
+  }
+}
+
+void launch_bed_to_presence(const uint8_t* payload, int64_t n, int64_t m, uint8_t* pres, int64_t rowb, hipStream_t s) {
+  const int64_t total = rowb * m;
+  if (total <= 0) return;
+  const int64_t blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(k_bed_to_presence, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, payload,
+                     n, m, pres, rowb);
+}
+
+// missing calls of markers j0 .. j0 + m: n minus the popcount of the presence row (as k_col_stats)
+__global__ void __launch_bounds__(256) k_missing_counts(const uint8_t* __restrict__ pres, int64_t rowb, int64_t n,
+                                                        int64_t j0, int32_t* __restrict__ out) {
+  __shared__ int32_t red[4];
+  const uint32_t* row = reinterpret_cast<const uint32_t*>(pres + (j0 + blockIdx.x) * rowb);  // rowb is a multiple of 16
+  int32_t c = 0;
+  for (int64_t w = threadIdx.x; w < rowb / 4; w += blockDim.x) c += __builtin_popcount(row[w] & 0x55555555u);
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = (int32_t)(n - (red[0] + red[1] + red[2] + red[3]));
+}
+
+void launch_missing_counts(const uint8_t* pres, int64_t rowb, int64_t n, int64_t j0, int64_t m, int32_t* out,
+                           hipStream_t s) {
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_missing_counts, dim3((unsigned)m), dim3(256), 0, s, pres, rowb, n, j0, out);
+}
+
+// ---------------------------------------------------------------------------
 // column statistics (bed.rs:231-242): mean and population std, from exact
 // integer sums over the 2-bit rows (more accurate than the reference's
 // sequential f32 sums).  One workgroup per marker; the two bit planes of a

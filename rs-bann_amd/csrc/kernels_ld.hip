@@ -28,6 +28,15 @@
 // so every line is fetched once per workgroup and whole.  K is split over
 // workgroups (blockIdx.y) and combined with int32 atomicAdd into the S band:
 // exact and order-independent.
+//
+// The pairwise-complete r2 (bann.h: a pair's missing individuals left out, as
+// PLINK does) needs five more bands of the same shape, with the presence image
+// (kernels_data.hip: field 1 = the call is there) on one or both sides and the
+// genotype field squared on one: N, a, b, qa, qb.  The kernel body is a template
+// over what each side stages and how it decodes a field (ld_band_tile<RA, RB>);
+// k_ld_band is its <genotype, genotype> case, k_ld_band_pw<RA, RB> the other
+// five, one launch each: the kernel is bound by decode and MFMA issue, not by
+// loads, and six accumulator sets do not fit two waves per SIMD.
 #include "bann_internal.h"
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -83,19 +92,28 @@ __device__ __forceinline__ uint4 ld_load16(const uint8_t* __restrict__ raw, int6
   return (j < M && off < rowb) ? *reinterpret_cast<const uint4*>(raw + j * rowb + off) : make_uint4(0, 0, 0, 0);
 }
 
-template <int P>
+// what one side of a product is: the genotype image's field, the presence image's field (0 / 1), or
+// the genotype field squared: on packed bytes of {0,1,2}, x + (x & 0x02020202) gives {0,1,4}
+enum { LD_G = 0, LD_P = 1, LD_G2 = 2 };
+
+template <int P, int SIDE>
 __device__ __forceinline__ v4i ld_field(const uint4 x) {
-  return v4i{(int)((x.x >> (2 * P)) & 0x03030303u), (int)((x.y >> (2 * P)) & 0x03030303u),
-             (int)((x.z >> (2 * P)) & 0x03030303u), (int)((x.w >> (2 * P)) & 0x03030303u)};
+  uint32_t v[4] = {(x.x >> (2 * P)) & 0x03030303u, (x.y >> (2 * P)) & 0x03030303u, (x.z >> (2 * P)) & 0x03030303u,
+                   (x.w >> (2 * P)) & 0x03030303u};
+  if constexpr (SIDE == LD_G2) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] += v[i] & 0x02020202u;
+  }
+  return v4i{(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
 }
 
-template <int P>
+template <int P, int RA, int RB>
 __device__ __forceinline__ void ld_mma(const LdFrag& f, v4i (&acc)[4][4]) {
   v4i A[4], B[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    A[t] = ld_field<P>(f.a[t]);
-    B[t] = ld_field<P>(f.b[t]);
+    A[t] = ld_field<P, RA>(f.a[t]);
+    B[t] = ld_field<P, RB>(f.b[t]);
   }
 #pragma unroll
   for (int ta = 0; ta < 4; ++ta)
@@ -103,9 +121,12 @@ __device__ __forceinline__ void ld_mma(const LdFrag& f, v4i (&acc)[4][4]) {
     for (int tb = 0; tb < 4; ++tb) acc[ta][tb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[ta], B[tb], acc[ta][tb], 0, 0, 0);
 }
 
-__global__ void __launch_bounds__(256, 2) k_ld_band(const uint8_t* __restrict__ raw, int64_t rowb, int64_t M,
-                                                    int64_t row0, int32_t rows, int32_t window, int32_t ncol,
-                                                    int32_t ksteps, int32_t kchunk, int32_t* __restrict__ S) {
+// the band of sum_i A_ij B_ik: the row markers' lines come from img_a and are decoded as RA, the column
+// markers' from img_b as RB (both images have the cohort image's layout)
+template <int RA, int RB>
+__device__ __forceinline__ void ld_band_tile(const uint8_t* __restrict__ img_a, const uint8_t* __restrict__ img_b,
+                                             int64_t rowb, int64_t M, int64_t row0, int32_t rows, int32_t window,
+                                             int32_t ncol, int32_t ksteps, int32_t kchunk, int32_t* __restrict__ S) {
   // one K stage (512 individuals = 128 B = 8 pieces of 16 B per marker) of the 128 row and the 128
   // column markers; piece p of row R sits at p ^ ((R >> 1) & 7): the stores of a row and the
   // ds_read_b128 lane groups of a fragment both meet every bank once
@@ -134,7 +155,8 @@ __global__ void __launch_bounds__(256, 2) k_ld_band(const uint8_t* __restrict__ 
   auto gload = [&](int t) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-      pre[i] = ld_load16(raw, rowb, M, (i < 4 ? ja : kb) + lrow + 32 * (i & 3), (int64_t)t * 128 + 16 * lpiece);
+      pre[i] = ld_load16(i < 4 ? img_a : img_b, rowb, M, (i < 4 ? ja : kb) + lrow + 32 * (i & 3),
+                         (int64_t)t * 128 + 16 * lpiece);
   };
   gload(t_begin);
   for (int t = t_begin; t < t_end; ++t) {
@@ -156,10 +178,10 @@ __global__ void __launch_bounds__(256, 2) k_ld_band(const uint8_t* __restrict__ 
           f.a[q] = tile[0][Ra][(4 * u + s) ^ ((Ra >> 1) & 7)];
           f.b[q] = tile[1][Rb][(4 * u + s) ^ ((Rb >> 1) & 7)];
         }
-        ld_mma<0>(f, acc);
-        ld_mma<1>(f, acc);
-        ld_mma<2>(f, acc);
-        ld_mma<3>(f, acc);
+        ld_mma<0, RA, RB>(f, acc);
+        ld_mma<1, RA, RB>(f, acc);
+        ld_mma<2, RA, RB>(f, acc);
+        ld_mma<3, RA, RB>(f, acc);
       }
     }
   }
@@ -176,22 +198,68 @@ __global__ void __launch_bounds__(256, 2) k_ld_band(const uint8_t* __restrict__ 
       }
 }
 
+__global__ void __launch_bounds__(256, 2) k_ld_band(const uint8_t* __restrict__ raw, int64_t rowb, int64_t M,
+                                                    int64_t row0, int32_t rows, int32_t window, int32_t ncol,
+                                                    int32_t ksteps, int32_t kchunk, int32_t* __restrict__ S) {
+  ld_band_tile<LD_G, LD_G>(raw, raw, rowb, M, row0, rows, window, ncol, ksteps, kchunk, S);
+}
+
+// the five further sums of the pairwise-complete r2 (bann.h): RA / RB name the row and the column side
+template <int RA, int RB>
+__global__ void __launch_bounds__(256, 2) k_ld_band_pw(const uint8_t* __restrict__ raw,
+                                                       const uint8_t* __restrict__ pres, int64_t rowb, int64_t M,
+                                                       int64_t row0, int32_t rows, int32_t window, int32_t ncol,
+                                                       int32_t ksteps, int32_t kchunk, int32_t* __restrict__ out) {
+  ld_band_tile<RA, RB>(RA == LD_P ? pres : raw, RB == LD_P ? pres : raw, rowb, M, row0, rows, window, ncol, ksteps,
+                       kchunk, out);
+}
+
+namespace {
+struct LdGrid {
+  int32_t ncol, ksteps, kchunk;
+  dim3 grid;
+};
+}  // namespace
+
+static LdGrid ld_grid(int64_t rowb, int32_t rows, int32_t window, int32_t ksplit_target) {
+  LdGrid g;
+  g.ncol = (127 + window) / 128 + 1;  // column tiles from the row tile to the one holding j + window
+  const int32_t nrt = (rows + 127) / 128;
+  g.ksteps = (int32_t)((rowb + 127) / 128);  // K stages of 512 individuals
+  const int64_t pairs = (int64_t)nrt * g.ncol;
+  // K split: enough workgroups for the device, at least 4 K stages per chunk where the cohort has them
+  int64_t split = (ksplit_target + pairs - 1) / pairs;
+  const int64_t max_split = (g.ksteps + 3) / 4;
+  if (split > max_split) split = max_split;
+  if (split < 1) split = 1;
+  g.kchunk = (int32_t)((g.ksteps + split - 1) / split);
+  const int32_t ny = (g.ksteps + g.kchunk - 1) / g.kchunk;
+  g.grid = dim3((unsigned)pairs, (unsigned)ny);
+  return g;
+}
+
 void launch_ld_band(const uint8_t* raw, int64_t rowb, int64_t M, int64_t row0, int32_t rows, int32_t window,
                     int32_t ksplit_target, int32_t* S, hipStream_t s) {
   if (rows <= 0 || window <= 0) return;
-  const int32_t ncol = (127 + window) / 128 + 1;  // column tiles from the row tile to the one holding j + window
-  const int32_t nrt = (rows + 127) / 128;
-  const int32_t ksteps = (int32_t)((rowb + 127) / 128);  // K stages of 512 individuals
-  const int64_t pairs = (int64_t)nrt * ncol;
-  // K split: enough workgroups for the device, at least 4 K stages per chunk where the cohort has them
-  int64_t split = (ksplit_target + pairs - 1) / pairs;
-  const int64_t max_split = (ksteps + 3) / 4;
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  const int32_t kchunk = (int32_t)((ksteps + split - 1) / split);
-  const int32_t ny = (ksteps + kchunk - 1) / kchunk;
-  hipLaunchKernelGGL(k_ld_band, dim3((unsigned)pairs, (unsigned)ny), dim3(256), 0, s, raw, rowb, M, row0, rows,
-                     window, ncol, ksteps, kchunk, S);
+  const LdGrid g = ld_grid(rowb, rows, window, ksplit_target);
+  hipLaunchKernelGGL(k_ld_band, g.grid, dim3(256), 0, s, raw, rowb, M, row0, rows, window, g.ncol, g.ksteps, g.kchunk,
+                     S);
+}
+
+// bands[b * stride ..], b = LD_BAND_N, _A, _B, _QA, _QB (bann_internal.h); the S band is launch_ld_band's
+void launch_ld_band_pw(const uint8_t* raw, const uint8_t* pres, int64_t rowb, int64_t M, int64_t row0, int32_t rows,
+                       int32_t window, int32_t ksplit_target, int32_t* bands, int64_t stride, hipStream_t s) {
+  if (rows <= 0 || window <= 0) return;
+  const LdGrid g = ld_grid(rowb, rows, window, ksplit_target);
+#define LD_PW(RA, RB, B)                                                                                          \
+  hipLaunchKernelGGL((k_ld_band_pw<RA, RB>), g.grid, dim3(256), 0, s, raw, pres, rowb, M, row0, rows, window, g.ncol, \
+                     g.ksteps, g.kchunk, bands + (B) * stride)
+  LD_PW(LD_P, LD_P, LD_BAND_N);
+  LD_PW(LD_G, LD_P, LD_BAND_A);
+  LD_PW(LD_P, LD_G, LD_BAND_B);
+  LD_PW(LD_G2, LD_P, LD_BAND_QA);
+  LD_PW(LD_P, LD_G2, LD_BAND_QB);
+#undef LD_PW
 }
 
 // ---------------------------------------------------------------------------
@@ -268,4 +336,78 @@ void launch_ld_mask(const int32_t* S, int32_t rows, int32_t window, int32_t word
   const int64_t blocks = (total + 255) / 256;
   hipLaunchKernelGGL(k_ld_mask, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, S, rows, window,
                      words, row0, M, n, stat0, st, qt, r2_min, chrom, bp, max_bp, mask);
+}
+
+// ---------------------------------------------------------------------------
+// the pairwise-complete r2 (bann.h): six bands of the block, band b at bands[b * stride]
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double ld_r2_pw(const int32_t* __restrict__ bands, int64_t stride, int64_t e) {
+  const int64_t N = bands[LD_BAND_N * stride + e], a = bands[LD_BAND_A * stride + e], b = bands[LD_BAND_B * stride + e];
+  const int64_t qa = bands[LD_BAND_QA * stride + e], qb = bands[LD_BAND_QB * stride + e], S = bands[LD_BAND_S * stride + e];
+  const int64_t va = N * qa - a * a, vb = N * qb - b * b;
+  if (va == 0 || vb == 0) return 0.0;
+  const int64_t cov = N * S - a * b;
+  const double num = (double)cov * (double)cov;
+  const double den = (double)va * (double)vb;
+  return num / den;
+}
+
+// in place: the int32 S band of the block becomes its f32 r2 band (0 where j + d >= M); the N band stays as
+// it is (0 where j + d >= M: nothing was added there)
+__global__ void __launch_bounds__(256) k_ld_r2_pw(int32_t* __restrict__ bands, int64_t stride, int64_t total,
+                                                  int32_t window, int64_t row0, int64_t M) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t jl = e / window;
+    const int64_t k = row0 + jl + (e - jl * window) + 1;
+    float out = 0.f;
+    if (k < M) out = (float)ld_r2_pw(bands, stride, e);
+    reinterpret_cast<float*>(bands + LD_BAND_S * stride)[e] = out;
+  }
+}
+
+void launch_ld_r2_pw(int32_t* bands, int64_t stride, int32_t rows, int32_t window, int64_t row0, int64_t M,
+                     hipStream_t s) {
+  const int64_t total = (int64_t)rows * window;
+  if (total <= 0) return;
+  const int64_t blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(k_ld_r2_pw, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, bands, stride,
+                     total, window, row0, M);
+}
+
+// k_ld_mask on the pairwise-complete r2; chrom and bp start at marker stat0
+__global__ void __launch_bounds__(256) k_ld_mask_pw(const int32_t* __restrict__ bands, int64_t stride, int32_t rows,
+                                                    int32_t window, int32_t words, int64_t row0, int64_t M,
+                                                    int64_t stat0, double r2_min, const int32_t* __restrict__ chrom,
+                                                    const int64_t* __restrict__ bp, int64_t max_bp,
+                                                    uint32_t* __restrict__ mask) {
+  const int64_t total = (int64_t)rows * words;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t jl = e / words;
+    const int32_t wd = (int32_t)(e - jl * words);
+    const int64_t j = row0 + jl;
+    uint32_t bits = 0;
+    for (int b = 0; b < 32; ++b) {
+      const int32_t d = 32 * wd + b + 1;
+      const int64_t k = j + d;
+      if (d > window || k >= M) break;
+      bool edge = ld_r2_pw(bands, stride, jl * window + d - 1) >= r2_min;
+      if (edge && chrom) {
+        const int64_t bj = bp[j - stat0], bk = bp[k - stat0];
+        const int64_t dist = bk > bj ? bk - bj : bj - bk;
+        edge = chrom[j - stat0] == chrom[k - stat0] && (max_bp <= 0 || dist <= max_bp);
+      }
+      bits |= (uint32_t)edge << b;
+    }
+    mask[e] = bits;
+  }
+}
+
+void launch_ld_mask_pw(const int32_t* bands, int64_t stride, int32_t rows, int32_t window, int32_t words, int64_t row0,
+                       int64_t M, int64_t stat0, double r2_min, const int32_t* chrom, const int64_t* bp, int64_t max_bp,
+                       uint32_t* mask, hipStream_t s) {
+  const int64_t total = (int64_t)rows * words;
+  if (total <= 0) return;
+  const int64_t blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(k_ld_mask_pw, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, bands, stride,
+                     rows, window, words, row0, M, stat0, r2_min, chrom, bp, max_bp, mask);
 }

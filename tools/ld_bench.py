@@ -12,8 +12,16 @@ MAC/s = n M window / t against the dense int8 MFMA peak.  One JSON line per wind
                      numpy int64 on the host (at most 16 threads), checked bit for bit against the
                      device band and EXTRAPOLATED linearly in M to the full cohort
   --host-only        the comparison arm alone on a numpy cohort of the same shape (needs no device)
+  --pairwise RATE    the pairwise-complete band against the plain one on one context: a numpy cohort
+                     with every call missing independently at RATE, encoded to a .bed payload and
+                     loaded with keep_missing + upload_bed; per window one warm-up call, then --reps
+                     calls of ld_band and of ld_band(pairwise=True).  The M marker rows are drawn with
+                     replacement from --pool distinct random markers (drawing 5e9 calls one by one
+                     would take minutes; the kernels' time does not depend on the values).  --out FILE
+                     also writes the records as one JSON document.
 
   python tools/ld_bench.py [--n 50000] [--markers 100000] [--windows 500,100] [--reps 3] [--host-markers 0]
+  python tools/ld_bench.py --pairwise 0.02 [--pool 4096] [--out profiles/ld_pairwise.json]
 """
 import argparse
 import json
@@ -63,6 +71,64 @@ def spread(ts):
             "spread_pct": round(100.0 * (max(ts) - min(ts)) / min(ts), 2)}
 
 
+def pairwise_arm(args, n, M, windows):
+    from bann import BannContext
+    from bann.io import encode_bed_payload
+    rng = np.random.default_rng(1000003)
+    P = min(args.pool, M)
+    bpc = (n + 3) // 4
+    pool = np.zeros((P, bpc), np.uint8)
+    missing = 0
+    for p0 in range(0, P, 256):
+        m = min(256, P - p0)
+        g = rng.binomial(2, rng.uniform(0.01, 0.5, size=(m, 1)), size=(m, n)).astype(np.int8)
+        miss = rng.random((m, n)) < args.pairwise
+        g[miss] = -1
+        missing += int(miss.sum())
+        pool[p0:p0 + m] = np.frombuffer(encode_bed_payload(g), np.uint8).reshape(m, bpc)
+    pick = rng.integers(0, P, size=M)
+    payload = pool[pick]
+    ctx = BannContext(0)
+    ctx.keep_missing()
+    ctx.upload_bed(payload.tobytes(), n, M)
+    del payload
+    counts = ctx.missing_counts()
+    lib, h = ctx._lib, ctx._h
+
+    def timed(f, *a, **kw):
+        lib.bann_synchronize(h)
+        t0 = time.perf_counter()
+        r = f(*a, **kw)
+        lib.bann_synchronize(h)
+        return (time.perf_counter() - t0) * 1e3, ctx.ld_timing(), r
+
+    recs = []
+    for w in windows:
+        arms = {}
+        for name, kw in (("plain", {}), ("pairwise", {"pairwise": True})):
+            timed(ctx.ld_band, w, **kw)  # warm-up
+            host, kern = [], []
+            for _ in range(args.reps):
+                t, k, band = timed(ctx.ld_band, w, **kw)
+                host.append(t)
+                kern.append(k)
+                del band
+            arms[name] = (kern, host)
+        rec = {"arm": "pairwise against plain ld_band", "n": n, "markers": M, "window": w,
+               "missing_rate": args.pairwise, "pool_markers": P, "missing_calls": int(counts.sum()),
+               "plain_kernel_ms": spread(arms["plain"][0]), "plain_host_ms": spread(arms["plain"][1]),
+               "pairwise_kernel_ms": spread(arms["pairwise"][0]), "pairwise_host_ms": spread(arms["pairwise"][1]),
+               "kernel_ratio_best": round(min(arms["pairwise"][0]) / min(arms["plain"][0]), 3),
+               "image_bytes": int((n + 63) // 64 * 16) * M}
+        recs.append(rec)
+        print(json.dumps(rec), flush=True)
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/ld_bench.py --pairwise", "records": recs}, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=50000)
@@ -71,9 +137,15 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--host-markers", type=int, default=0)
     ap.add_argument("--host-only", action="store_true")
+    ap.add_argument("--pairwise", type=float, default=None, metavar="RATE")
+    ap.add_argument("--pool", type=int, default=4096)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     n, M = args.n, args.markers
     windows = [int(w) for w in args.windows.split(",")]
+    if args.pairwise is not None:
+        pairwise_arm(args, n, M, windows)
+        return
     if args.host_only:
         rng = np.random.default_rng(1000003)
         for w in windows:
