@@ -196,6 +196,63 @@ int bann_genotypes_ld_band_pairwise(bann_ctx* ctx, int32_t window, int64_t first
 int bann_genotypes_ld_graph_pairwise(bann_ctx* ctx, int32_t window, float r2_min, const int32_t* chrom,
                                      const int64_t* bp, int64_t max_bp, int64_t* num_edges);
 
+/* ---------------- linear scores, the linear-model simulator, cohorts for simulate-xy ----------------
+ * K linear scores of the whole cohort from one pass over the resident 2-bit image
+ * (LinearModel::predict, linear_model.rs:121-134, for K effect vectors at once).  offsets / markers:
+ * a grouping as bann_grouping_read / bann_grouping_uniform return it, E = offsets[num_groups] entries;
+ * groups may overlap.  effects [K][E], out [K][n]:
+ *   out[k][i] = sum over the entries t in file order of effects[k][t] (g(i, markers[t]) - mu) / sigma
+ * with the context's mu and sigma (bann_genotypes_stats, or what bann_genotypes_set_stats installed); a
+ * marker with sigma = 0 contributes 0; a 2-bit field counts as its integer value 0..3, so a missing
+ * call reads 0 with bann_genotypes_keep_missing on or off, as in training.  Needs a loaded cohort, no
+ * branches and no bann_finalize; BANN_E_STATE after a bann_finalize that freed the image; BANN_E_ARG
+ * for K outside [1, 65535], a marker index outside the cohort or offsets that decrease.
+ * The entries are cut into chunks of bann_genotypes_linear_chunk entries (default 2048); inside a
+ * chunk one f32 accumulator per (individual, column) adds w[k][t] g with w = effects / sigma (f32) by
+ * one fused multiply-add per entry, in file order; the chunks' partial sums and the offset
+ * c_k = -sum_t w[k][t] mu_t (f64, fixed-order tree) are added in f64 in ascending chunk order and
+ * rounded to f32 once.  Bitwise reproducible; a column's bits depend on its effects, the cohort and the
+ * chunk length alone, not on K, its position among the columns or the other columns. */
+int bann_genotypes_linear_score(bann_ctx* ctx, int32_t num_groups, const int64_t* offsets, const int32_t* markers,
+                                const float* effects, int32_t K, float* out);
+/* entries per chunk of the score (0 restores the default): a test hook, as bann_genotypes_ld_scratch_limit */
+int bann_genotypes_linear_chunk(bann_ctx* ctx, int64_t entries_per_chunk);
+/* HIP-event milliseconds of the device kernels of the last linear_score / bann_linear_simulate_y call */
+int bann_genotypes_linear_timing(const bann_ctx* ctx, double* kernel_ms);
+/* LinearModelBuilder::with_random_effects (linear_model.rs:46-91) with the library's counter-based
+ * draws.  Inclusion is over the E entries of the whole model: num_effective = e >= 0 keeps entry t iff
+ * fewer than e entries come before it in the order of (key_t, t), key_t = word 0 of the Philox block
+ * of stream (seed, INCLUDE) at counter t (exactly e survive; e > E and e = 0: BANN_E_ARG); otherwise
+ * proportion_effective = p >= 0 keeps t iff u01(key_t) < p; neither set (both < 0): every entry.
+ * sd = sqrtf(h / (float)m_incl) in f32; a kept entry is sd * (float)z_t, z_t standard normal number t
+ * of stream (seed, EFFECT); a dropped entry is 0.  *m_incl (nullable) = the count, formed on the
+ * device.  BANN_E_ARG for m_incl = 0 ("no effective marker"), h outside (0, 1], E outside [1, 2^32).
+ * The context gives the device only: no cohort is needed. */
+int bann_linear_effects(bann_ctx* ctx, int64_t E, float heritability, int64_t num_effective, float proportion_effective,
+                        uint64_t seed, float* effects_out, int64_t* m_incl);
+/* the tail of simulate_y_linear (rs-bann.rs:578-606) for K columns: g = the scores above, then per
+ * column the fixed-order two-pass f64 moments of g, rv = s2 (1 / h - 1) with s2 the sample variance
+ * (n - 1), y_i = g_i + (float)(sqrt(rv) z_i) with z_i of stream (seeds[k], NOISE), and the moments of
+ * y: bann_net_simulate_y's kernels and bits.  y_out [K][n]; g_out [K][n] or NULL; stats [K][5] =
+ * {sum g, sum (g - mean g)^2, sum y, sum (y - mean y)^2, rv}.  h = 1: y = g and rv = 0.  Nothing waits
+ * on the host between the first launch and the copies back.  Errors: the score's; BANN_E_ARG for h
+ * outside (0, 1]; BANN_E_SHAPE for n < 2. */
+int bann_linear_simulate_y(bann_ctx* ctx, int32_t num_groups, const int64_t* offsets, const int32_t* markers,
+                           const float* effects, int32_t K, float heritability, const uint64_t* seeds, float* y_out,
+                           float* g_out, double* stats);
+/* bann_genotypes_synthetic with the allele frequency of marker j given as maf[j] instead of drawn
+ * (BedVM::random(.., Some(mafs), ..), bed.rs:136-188): g_ij ~ Binomial(2, maf[j]) from the same
+ * streams, zero-variance markers redrawn up to the same 64 attempts.  The train and the test cohort
+ * of a simulation share maf and differ in seed. */
+int bann_genotypes_synthetic_maf(bann_ctx* ctx, int64_t n, int64_t num_markers, const float* maf, uint64_t seed);
+/* BedVM::to_file (bed.rs:248-264): stem.bed = the three signature bytes and ceil(n/4) bytes per
+ * marker, encoded on the device (2 -> 00, 1 -> 10, 0 -> 11, and 01 where a presence image is kept
+ * and says the call is absent; padding bits 0) and written through a bounded staging buffer;
+ * stem.dims = "{n}\t{M}" without a newline.  BANN_E_ARG for a field value 3 (only
+ * bann_genotypes_upload can produce one) or a file that cannot be written; BANN_E_STATE without a
+ * resident image. */
+int bann_genotypes_save_bed(bann_ctx* ctx, const char* stem);
+
 /* ---------------- files on either side of the path (host only, no device) ---------------- */
 /* BedDims (io/dims.rs:15-34): stem.dims "n M", else the .fam / .bim line counts */
 int bann_bed_dims(const char* stem, int64_t* n_out, int64_t* num_markers_out);

@@ -113,6 +113,15 @@ SIGNATURES = {
     "bann_genotypes_ld_band_pairwise": (C.c_int, [_P, _i32, _i64, _i64, _pf32, _pi32]),
     "bann_genotypes_ld_graph_pairwise": (C.c_int, [_P, _i32, _f32, _pi32, C.POINTER(_i64), _i64,
                                                    C.POINTER(_i64)]),
+    # linear scores from the resident image, the linear-model simulator, cohorts for simulate-xy
+    "bann_genotypes_linear_score": (C.c_int, [_P, _i32, C.POINTER(_i64), _pi32, _pf32, _i32, _pf32]),
+    "bann_genotypes_linear_chunk": (C.c_int, [_P, _i64]),
+    "bann_genotypes_linear_timing": (C.c_int, [_P, _pf64]),
+    "bann_linear_effects": (C.c_int, [_P, _i64, _f32, _i64, _f32, _u64, _pf32, C.POINTER(_i64)]),
+    "bann_linear_simulate_y": (C.c_int, [_P, _i32, C.POINTER(_i64), _pi32, _pf32, _i32, _f32, C.POINTER(_u64), _pf32,
+                                         _pf32, _pf64]),
+    "bann_genotypes_synthetic_maf": (C.c_int, [_P, _i64, _i64, _pf32, _u64]),
+    "bann_genotypes_save_bed": (C.c_int, [_P, C.c_char_p]),
     "bann_io_last_error": (C.c_char_p, []),
     "bann_bim_read": (C.c_int, [C.c_char_p, C.POINTER(_i64), _pi32, C.POINTER(_i64)]),
     "bann_ld_graph_read_plink": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_i64), C.POINTER(_i64),

@@ -9,6 +9,7 @@ nothing here computes on the CPU.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Sequence
 
 import numpy as np
@@ -86,9 +87,22 @@ class BannContext:
         from .io import bed_dims
         self.n, self.num_markers = bed_dims(stem)
 
-    def synthetic_genotypes(self, n: int, num_markers: int, seed: int = 42):
-        self._check(self._lib.bann_genotypes_synthetic(self._h, n, num_markers, seed))
+    def synthetic_genotypes(self, n: int, num_markers: int, seed: int = 42, mafs=None):
+        """g_ij ~ Binomial(2, p_j) on the device; p_j drawn per marker, or mafs[j] when given (the train
+        and the test cohort of a simulation share mafs and differ in seed)."""
+        if mafs is None:
+            self._check(self._lib.bann_genotypes_synthetic(self._h, n, num_markers, seed))
+        else:
+            p = _f32(mafs)
+            if p.shape != (num_markers,):
+                raise ValueError("mafs needs one entry per marker")
+            self._check(self._lib.bann_genotypes_synthetic_maf(self._h, n, num_markers, _ptr(p, C.c_float), seed))
         self.n, self.num_markers = n, num_markers
+
+    def save_bed(self, stem: str):
+        """the resident cohort as stem.bed + stem.dims (BedVM::to_file, bed.rs:248-264); a call the
+        presence image (keep_missing) records as absent is written as missing."""
+        self._check(self._lib.bann_genotypes_save_bed(self._h, os.fspath(stem).encode()))
 
     def genotype_stats(self):
         mu = np.zeros(self.num_markers, np.float32)
@@ -175,6 +189,81 @@ class BannContext:
         """HIP-event milliseconds of the device kernels of the last ld_band / ld_graph call, pairwise or not."""
         ms = C.c_double()
         self._check(self._lib.bann_genotypes_ld_timing(self._h, C.byref(ms)))
+        return ms.value
+
+    # ---------------------------------------------------------- linear model
+    @staticmethod
+    def _linear_args(groups, effects):
+        gl = [np.asarray(g, dtype=np.int32).ravel() for g in groups]
+        off = np.zeros(len(gl) + 1, np.int64)
+        off[1:] = np.cumsum([g.size for g in gl])
+        mk = np.ascontiguousarray(np.concatenate(gl) if gl else np.zeros(0, np.int32), dtype=np.int32)
+        eff = _f32(effects)
+        single = eff.ndim == 1
+        eff = np.ascontiguousarray(eff.reshape(1, -1) if single else eff)
+        if eff.ndim != 2 or eff.shape[1] != mk.size:
+            raise ValueError(f"effects are [E] or [K, E] with E = {mk.size} grouping entries")
+        if mk.size == 0:
+            mk = np.zeros(1, np.int32)
+        return len(gl), off, mk, eff, single
+
+    def linear_score(self, groups, effects) -> np.ndarray:
+        """f32 [n] or [K, n]: sum over the grouping's entries t (group by group, overlaps counted once per
+        entry) of effects[k][t] (g(i, marker_t) - mu) / sigma, K columns from one pass over the resident
+        2-bit image (LinearModel::predict, linear_model.rs:121-134); needs no branches and no finalize.
+        effects: [E] or [K, E]."""
+        G, off, mk, eff, single = self._linear_args(groups, effects)
+        out = np.zeros((eff.shape[0], self.n), np.float32)
+        self._check(self._lib.bann_genotypes_linear_score(self._h, G, _ptr(off, C.c_int64), _ptr(mk, C.c_int32),
+                                                          _ptr(eff, C.c_float), eff.shape[0], _ptr(out, C.c_float)))
+        return out[0] if single else out
+
+    def linear_effects(self, num_entries: int, heritability: float, num_effective: Optional[int] = None,
+                       proportion_effective: Optional[float] = None, seed: int = 0):
+        """(effects f32 [E], m_incl): LinearModelBuilder::with_random_effects (linear_model.rs:46-91) with
+        the library's counter-based draws; num_effective takes precedence over proportion_effective."""
+        out = np.zeros(max(int(num_entries), 1), np.float32)
+        m = C.c_int64()
+        self._check(self._lib.bann_linear_effects(
+            self._h, int(num_entries), float(heritability), -1 if num_effective is None else int(num_effective),
+            -1.0 if proportion_effective is None else float(proportion_effective), int(seed), _ptr(out, C.c_float),
+            C.byref(m)))
+        return out[:int(num_entries)], m.value
+
+    def linear_simulate_y(self, groups, effects, heritability: float, seeds, return_g: bool = False):
+        """(y, stats) or (y, g, stats): phenotypes under K linear models from one score pass, the tail of
+        simulate_y_linear (rs-bann.rs:578-606) per column with noise stream seeds[k].  effects [E] or
+        [K, E], seeds an int or K ints.  stats: one dict per column (a single dict for [E]) with
+        bann_net_simulate_y's mean / variance / env_variance and the raw f64 sums under "sums" =
+        (sum g, sum (g - mean)^2, sum y, sum (y - mean)^2, residual variance)."""
+        G, off, mk, eff, single = self._linear_args(groups, effects)
+        K = eff.shape[0]
+        sd = np.ascontiguousarray(np.atleast_1d(np.asarray(seeds, dtype=np.uint64)))
+        if sd.shape != (K,):
+            raise ValueError("one noise seed per column")
+        y = np.zeros((K, self.n), np.float32)
+        g = np.zeros((K, self.n), np.float32) if return_g else None
+        st = np.zeros((K, 5), np.float64)
+        self._check(self._lib.bann_linear_simulate_y(
+            self._h, G, _ptr(off, C.c_int64), _ptr(mk, C.c_int32), _ptr(eff, C.c_float), K, float(heritability),
+            _ptr(sd, C.c_uint64), _ptr(y, C.c_float), _ptr(g, C.c_float) if return_g else None, _ptr(st, C.c_double)))
+        n = self.n
+        stats = [{"mean": float(np.float32(s[2] / n)), "variance": float(np.float32(s[3] / (n - 1))),
+                  "env_variance": float(np.float32(s[4])), "sums": tuple(float(v) for v in s)} for s in st]
+        if single:
+            y, stats = y[0], stats[0]
+            g = g[0] if return_g else None
+        return (y, g, stats) if return_g else (y, stats)
+
+    def linear_chunk(self, entries_per_chunk: int = 0):
+        """entries per chunk of linear_score (0: the default): the number of f32 terms one accumulator
+        sums before the f64 fold.  A test hook; a column's bits depend on it."""
+        self._check(self._lib.bann_genotypes_linear_chunk(self._h, int(entries_per_chunk)))
+
+    def linear_timing(self) -> float:
+        """HIP-event milliseconds of the device kernels of the last linear_score / linear_simulate_y call."""
+        ms = C.c_double()
+        self._check(self._lib.bann_genotypes_linear_timing(self._h, C.byref(ms)))
         return ms.value
 
     # -------------------------------------------------------------- branches

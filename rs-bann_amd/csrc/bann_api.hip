@@ -756,9 +756,30 @@ extern "C" int bann_genotypes_synthetic(bann_ctx* ctx, int64_t n, int64_t num_ma
   if (!ctx) return BANN_E_ARG;
   int rc = alloc_genotypes(ctx, n, num_markers);
   if (rc) return rc;
-  launch_synthetic_genotypes(ctx->d_g, ctx->rowb, ctx->d_mu, ctx->d_sigma, n, num_markers, seed, ctx->stream);
+  launch_synthetic_genotypes(ctx->d_g, ctx->rowb, ctx->d_mu, ctx->d_sigma, n, num_markers, nullptr, seed, ctx->stream);
   CK(hipGetLastError());
   CK(hipStreamSynchronize(ctx->stream));
+  return BANN_OK;
+}
+
+extern "C" int bann_genotypes_synthetic_maf(bann_ctx* ctx, int64_t n, int64_t num_markers, const float* maf,
+                                            uint64_t seed) {
+  if (!ctx) return BANN_E_ARG;
+  if (!maf) return fail(ctx, BANN_E_ARG, "maf is null");
+  for (int64_t j = 0; j < num_markers; ++j)
+    if (!(maf[j] >= 0.f && maf[j] <= 1.f)) return fail(ctx, BANN_E_ARG, "an allele frequency outside [0, 1]");
+  int rc = alloc_genotypes(ctx, n, num_markers);
+  if (rc) return rc;
+  float* d_maf = nullptr;
+  CK(dalloc(&d_maf, num_markers));
+  hipError_t e = hipMemcpyAsync(d_maf, maf, (size_t)num_markers * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    launch_synthetic_genotypes(ctx->d_g, ctx->rowb, ctx->d_mu, ctx->d_sigma, n, num_markers, d_maf, seed, ctx->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  dfree(d_maf);
+  CK(e);
   return BANN_OK;
 }
 

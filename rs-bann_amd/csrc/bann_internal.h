@@ -168,7 +168,9 @@ struct PackJob {
 __host__ __device__ inline bool tile_f3m1(int path) { return path == PATH_FX || path == PATH_FXL; }
 // genotype image: 2-bit variant-major rows of rowb = ceil(n/64)*16 bytes (kernels_data.hip header)
 void launch_synthetic_genotypes(uint8_t* raw, int64_t rowb, float* mu, float* sigma, int64_t n, int64_t M,
-                                uint64_t seed, hipStream_t s);
+                                const float* maf, uint64_t seed, hipStream_t s);  // maf null: drawn per marker
+void launch_raw_to_bed(const uint8_t* raw, const uint8_t* pres, int64_t rowb, int64_t n, int64_t j0, int64_t m,
+                       uint8_t* payload, int32_t* flag, hipStream_t s);
 void launch_i8_to_raw(const int8_t* g, int64_t n, int64_t m, uint8_t* raw, int64_t rowb, int32_t* flag,
                       hipStream_t s);
 void launch_bed_to_raw(const uint8_t* payload, int64_t n, int64_t m, uint8_t* raw, int64_t rowb, hipStream_t s);

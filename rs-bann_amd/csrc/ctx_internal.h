@@ -215,6 +215,10 @@ struct bann_ctx {
   // (bann_genotypes_ld_scratch_limit)
   int64_t ld_scratch = int64_t(128) << 20;
   double ld_ms = 0.0;  // HIP-event time of the device kernels of the last ld_band / ld_graph call, pairwise or not
+  // the linear score (kernels_lin.hip): entries per chunk (0: the default, bann_genotypes_linear_chunk) and
+  // the HIP-event time of the device kernels of the last score or linear simulate-y call
+  int64_t lin_chunk = 0;
+  double lin_ms = 0.0;
   // in-trajectory launch timing (bann_set_launch_timing): HIP events around every
   // gradient and update launch of the leapfrog sessions, resolved at bann_leapfrog_end
   bool tm_on = false;
@@ -311,6 +315,13 @@ int init_branches_net(bann_ctx* ctx, const bann_init_cfg* cfg, uint64_t seed, do
 // g = (0 + bias) + sum_b f_b in branch order (f32) at the context's parameters, y = g + noise, the
 // moments; bann_net_simulate_y without the net (include/bann_net.h)
 int simulate_y_device(bann_ctx* ctx, float bias, float heritability, uint64_t seed, float* y_out, float stats_out[3]);
+// kernels_init.hip, for kernels_lin.hip: simulate-y's moment and noise launches on a vector of the caller's.
+// part: sim_moment_blocks(n) doubles of scratch; sums[0] = sum x, sums[1] = sum (x - mean)^2; no host wait
+int64_t sim_moment_blocks(int64_t n);
+void sim_launch_moments(const float* x, int64_t n, double* part, double* sums, hipStream_t s);
+// y_i += (float)(sqrt(rv) z_i), rv = ss[0] / (n - 1) * inv_h_m1 also to *rv_out, z_i of stream (seed, NOISE)
+void sim_launch_noise(float* y, int64_t n, double inv_h_m1, const double* ss, uint64_t seed, double* rv_out,
+                      hipStream_t s);
 int net_buffers_init(bann_ctx* ctx);
 // network mode: k_forward_gsum's items for a persistent fx-only plan of 8-chunk branches
 int build_net_groups(bann_ctx* ctx, Plan& p);

@@ -16,6 +16,8 @@
 #define INIT_STREAM_THETA 0xB100000000000000ull   // | branch: the parameters, counter = entry / 4
 #define INIT_STREAM_SELECT 0xB200000000000000ull  // | branch: the marker keys, counter = marker
 #define INIT_STREAM_NOISE 0xB300000000000000ull   // the phenotype noise, counter = individual / 4
+#define INIT_STREAM_EFFECT 0xB400000000000000ull  // the linear model's effects (kernels_lin.hip), counter = entry / 4
+#define INIT_STREAM_INCLUDE 0xB500000000000000ull // its inclusion keys, counter = entry
 
 __host__ __device__ inline uint32_t init_word(const u32x4& r, uint32_t k) {
   return k == 0 ? r.x : (k == 1 ? r.y : (k == 2 ? r.z : r.w));
@@ -76,6 +78,12 @@ __host__ __device__ inline double init_normal(uint64_t seed, uint64_t stream, ui
 // selection key of marker j of a branch: word x of the block at counter j
 __host__ __device__ inline uint32_t init_select_key(uint64_t seed, int32_t branch, int32_t j) {
   return philox_bits(seed, INIT_STREAM_SELECT | (uint64_t)(uint32_t)branch, (uint64_t)j).x;
+}
+
+// inclusion key of entry t of a linear model (the concatenated entry list, not per branch): word x
+// of the block at counter t
+__host__ __device__ inline uint32_t init_include_key(uint64_t seed, uint64_t t) {
+  return philox_bits(seed, INIT_STREAM_INCLUDE, t).x;
 }
 
 // exact-count selection: marker j is kept iff fewer than e of the branch's markers come before

@@ -24,11 +24,12 @@
 // ---------------------------------------------------------------------------
 // synthetic cohort: g_ij ~ Binomial(2, p_j), p_j ~ U(0.01, 0.5); zero-variance
 // markers redrawn (bed.rs:136-188 semantics).  One workgroup per marker, one
-// byte (4 individuals, two Philox draws) per thread and step.
+// byte (4 individuals, two Philox draws) per thread and step.  maf non-null: p_j = maf[j], given
+// instead of drawn (bann_genotypes_synthetic_maf); the genotype streams are the same.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_synthetic(uint8_t* __restrict__ raw, int64_t rowb, float* __restrict__ mu,
                                                    float* __restrict__ sigma, int64_t n, int64_t M,
-                                                   uint64_t seed) {
+                                                   const float* __restrict__ maf, uint64_t seed) {
   __shared__ int64_t red[2][4];
   __shared__ int done;
   const int64_t j = blockIdx.x;
@@ -36,7 +37,7 @@ __global__ void __launch_bounds__(256) k_synthetic(uint8_t* __restrict__ raw, in
   uint8_t* row = raw + j * rowb;
   for (uint32_t attempt = 0;; ++attempt) {
     u32x4 pb = philox_bits(seed, 0xA11E1Eull + ((uint64_t)attempt << 40), (uint64_t)j);
-    const float p = 0.01f + 0.49f * u01(pb.x);
+    const float p = maf ? maf[j] : 0.01f + 0.49f * u01(pb.x);
     int64_t s1 = 0, s2 = 0;
     const uint64_t stream = ((uint64_t)j << 8) | attempt;
     for (int64_t q = threadIdx.x; q < rowb; q += blockDim.x) {
@@ -85,9 +86,9 @@ __global__ void __launch_bounds__(256) k_synthetic(uint8_t* __restrict__ raw, in
 }
 
 void launch_synthetic_genotypes(uint8_t* raw, int64_t rowb, float* mu, float* sigma, int64_t n, int64_t M,
-                                uint64_t seed, hipStream_t s) {
+                                const float* maf, uint64_t seed, hipStream_t s) {
   if (M <= 0) return;
-  hipLaunchKernelGGL(k_synthetic, dim3((unsigned)M), dim3(256), 0, s, raw, rowb, mu, sigma, n, M, seed);
+  hipLaunchKernelGGL(k_synthetic, dim3((unsigned)M), dim3(256), 0, s, raw, rowb, mu, sigma, n, M, maf, seed);
 }
 
 // ---------------------------------------------------------------------------
@@ -156,6 +157,44 @@ void launch_bed_to_raw(const uint8_t* payload, int64_t n, int64_t m, uint8_t* ra
   const int64_t blocks = (total + 255) / 256;
   hipLaunchKernelGGL(k_bed_to_raw, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, payload, n,
                      m, raw, rowb);
+}
+
+// ---------------------------------------------------------------------------
+// raw rows of markers j0 .. j0 + m -> .bed payload rows (bann_genotypes_save_bed): the inverse of the
+// LUT above, 2 -> 00, 1 -> 10, 0 -> 11, and 01 where the presence image (pres non-null) says the call
+// is absent; the codes past n in the last byte are 0; flag |= any field value 3
+// ---------------------------------------------------------------------------
+__global__ void k_raw_to_bed(const uint8_t* __restrict__ raw, const uint8_t* __restrict__ pres, int64_t rowb, int64_t n,
+                             int64_t j0, int64_t m, uint8_t* __restrict__ pl, int32_t* __restrict__ flag) {
+  const int64_t bpc = (n + 3) / 4;
+  const int64_t total = bpc * m;
+  int bad = 0;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t j = t / bpc, q = t - j * bpc;
+    const uint32_t byte = raw[(j0 + j) * rowb + q];
+    const uint32_t pm = pres ? pres[(j0 + j) * rowb + q] : 0xFFu;
+    uint32_t out = 0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      if (4 * q + p >= n) break;
+      const uint32_t v = (byte >> (2 * p)) & 3u;
+      bad |= v == 3u;
+      uint32_t c = v == 2u ? 0u : (v == 1u ? 2u : 3u);
+      if (!((pm >> (2 * p)) & 1u)) c = 1u;
+      out |= c << (2 * p);
+    }
+    pl[t] = (uint8_t)out;
+  }
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+
+void launch_raw_to_bed(const uint8_t* raw, const uint8_t* pres, int64_t rowb, int64_t n, int64_t j0, int64_t m,
+                       uint8_t* payload, int32_t* flag, hipStream_t s) {
+  const int64_t total = (n + 3) / 4 * m;
+  if (total <= 0) return;
+  const int64_t blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(k_raw_to_bed, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, raw, pres, rowb,
+                     n, j0, m, payload, flag);
 }
 
 // ---------------------------------------------------------------------------

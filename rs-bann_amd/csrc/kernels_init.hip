@@ -351,17 +351,27 @@ int64_t sim_blocks(int64_t n) { return (n + SIM_CHUNK - 1) / SIM_CHUNK; }
 
 // sums[0] = sum x, sums[1] = sum (x - mean)^2 on the device, no host wait
 void launch_moments(bann_ctx* ctx, const float* x, double* sums) {
-  const int64_t n = ctx->n;
-  const int32_t nblk = (int32_t)sim_blocks(n);
-  const dim3 blk(INIT_THREADS);
-  hipLaunchKernelGGL(k_sim_partial, dim3((unsigned)nblk), blk, 0, ctx->stream, x, n, 1, (const double*)nullptr,
-                     ctx->d_sim_part);
-  hipLaunchKernelGGL(k_sim_fold, dim3(1), blk, 0, ctx->stream, ctx->d_sim_part, nblk, sums);
-  hipLaunchKernelGGL(k_sim_partial, dim3((unsigned)nblk), blk, 0, ctx->stream, x, n, 2, sums, ctx->d_sim_part);
-  hipLaunchKernelGGL(k_sim_fold, dim3(1), blk, 0, ctx->stream, ctx->d_sim_part, nblk, sums + 1);
+  sim_launch_moments(x, ctx->n, ctx->d_sim_part, sums, ctx->stream);
 }
 
 }  // namespace
+
+int64_t sim_moment_blocks(int64_t n) { return sim_blocks(n); }
+
+void sim_launch_moments(const float* x, int64_t n, double* part, double* sums, hipStream_t s) {
+  const int32_t nblk = (int32_t)sim_blocks(n);
+  const dim3 blk(INIT_THREADS);
+  hipLaunchKernelGGL(k_sim_partial, dim3((unsigned)nblk), blk, 0, s, x, n, 1, (const double*)nullptr, part);
+  hipLaunchKernelGGL(k_sim_fold, dim3(1), blk, 0, s, part, nblk, sums);
+  hipLaunchKernelGGL(k_sim_partial, dim3((unsigned)nblk), blk, 0, s, x, n, 2, sums, part);
+  hipLaunchKernelGGL(k_sim_fold, dim3(1), blk, 0, s, part, nblk, sums + 1);
+}
+
+void sim_launch_noise(float* y, int64_t n, double inv_h_m1, const double* ss, uint64_t seed, double* rv_out,
+                      hipStream_t s) {
+  hipLaunchKernelGGL(k_sim_noise, dim3((unsigned)((n + INIT_THREADS - 1) / INIT_THREADS)), dim3(INIT_THREADS), 0, s, y, n,
+                     inv_h_m1, ss, seed, rv_out);
+}
 
 extern "C" int bann_init_branches(bann_ctx* ctx, const int32_t* branches, int32_t nb, const bann_init_cfg* cfg,
                                   uint64_t seed) {
@@ -409,8 +419,7 @@ int simulate_y_device(bann_ctx* ctx, float bias, float heritability, uint64_t se
   const bool noise = heritability != 1.f;
   if (noise) {
     launch_moments(ctx, y, sums);
-    hipLaunchKernelGGL(k_sim_noise, dim3((unsigned)((n + INIT_THREADS - 1) / INIT_THREADS)), dim3(INIT_THREADS), 0,
-                       ctx->stream, y, n, 1.0 / (double)heritability - 1.0, sums + 1, seed, sums + 4);
+    sim_launch_noise(y, n, 1.0 / (double)heritability - 1.0, sums + 1, seed, sums + 4, ctx->stream);
   }
   launch_moments(ctx, y, sums + 2);
   CK(hipGetLastError());
