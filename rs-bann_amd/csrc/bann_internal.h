@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define BANN_MAXL 8          // max layers per branch (hidden + summary + output)
 #define BANN_FUSED_MAXW 4    // fused kernels (fx, fxl): every layer width <= 4
 #define BANN_WIDE_MAXW 32    // wide fused kernel (wx): one hidden layer, W, S <= 32
@@ -105,7 +107,7 @@ struct FusedConst {
 
 struct DevState {
   const BranchDev* br;    // [nbranch]
-  const uint8_t* xu2;     // 2-bit genotype tile images of every branch ([tile][chunk][1 KiB], kernels_fx.hip)
+  const uint8_t* xu2;     // 2-bit genotype tile images of every branch ([tile][chunk][1 KiB], fx_tile.h)
   const uint8_t* xi;      // individual-major 2-bit images of the fx branches (kernels_fi.hip), or null
   const uint8_t* dig;     // digits
   FusedConst* fc;         // [nbranch]
@@ -155,6 +157,18 @@ struct DevState {
 };
 
 // ---- launchers (defined in the kernel translation units) ----
+// host: f(integral_constant<activation>) for the runtime activation of a launch, so that a generic
+// lambda names the kernel instantiation; activations past 3 are the identity's (4)
+template <class F>
+static inline void act_dispatch(int act, F&& f) {
+  switch (act) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
 // one chunk (64 marker rows) of one branch's tile image: batched pack (kernels_data.hip)
 struct PackJob {
   int64_t dst;          // byte offset of the chunk in tile 0 of the branch's image (x_off + 1024 c)
@@ -164,7 +178,7 @@ struct PackJob {
   int32_t f3m1;         // tile images only: field 3 (bits 6-7) stored as code - 1 (fx / fxl / fxh branches)
 };
 // the fx / fxl / fxh kernels read their tile images with field 3 stored as code - 1
-// (kernels_fx.hip header); the wide and layered kernels read plain codes
+// (fx_tile.h); the wide and layered kernels read plain codes
 __host__ __device__ inline bool tile_f3m1(int path) { return path == PATH_FX || path == PATH_FXL; }
 // genotype image: 2-bit variant-major rows of rowb = ceil(n/64)*16 bytes (kernels_data.hip header)
 void launch_synthetic_genotypes(uint8_t* raw, int64_t rowb, float* mu, float* sigma, int64_t n, int64_t M,
@@ -217,7 +231,7 @@ void launch_net_sum(const DevState& st, const int32_t* branches, int32_t nb, flo
 // k_forward_gsum): the same two-pass fixed-order sum; scratch: residual_delta_scratch_floats(n)
 void launch_net_sum_rows(const DevState& st, const float* rows, int32_t nrows, float* out, float* scratch,
                          hipStream_t s);
-// network-mode forward of fx branches of 8 chunks, one row per item (kernels_fx.hip); blist:
+// network-mode forward of fx branches of 8 chunks, one row per item (kernels_fx_gsum.hip); blist:
 // the items' branch lists; at most forward_gsum_max_tiles() tiles per item
 void launch_forward_gsum(const DevState& st, const NetGroupItem* items, int32_t nitems, const int32_t* blist,
                          int32_t L, int32_t act, float* gsum, hipStream_t s);
@@ -312,6 +326,10 @@ void launch_stats_fold(const DevState& st, const float* theta0, int64_t theta_st
 void launch_row_rss(const float* row, const float* y, int64_t n, double* out, hipStream_t s);
 void launch_fused_grad_fxl(const DevState& st, const GradItem* items, int32_t nitems, int32_t L, int32_t act,
                            int32_t nw, int32_t cpw, int full, int write_pred, int head, hipStream_t s);
+// the head-wave kernel (kernels_fxh.hip) for the fxl groups fxh_takes (fx_shapes.h): nc compute waves of
+// at most slot_kib chunks each; launch_fused_grad_fxl hands those groups on
+void launch_fused_grad_fxh(const DevState& st, const GradItem* items, int32_t nitems, int32_t L, int32_t act,
+                           int nc, int write_pred, int slot_kib, hipStream_t s);
 void launch_step_sizes(const DevState& st, const double* base, const int32_t* branches, int32_t nb, int32_t max_p,
                        int izmailov, float c, int32_t L, hipStream_t s);
 void launch_restore_pred(const DevState& st, const int32_t* branches, int32_t nb, hipStream_t s);

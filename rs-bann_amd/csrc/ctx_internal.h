@@ -90,7 +90,7 @@ struct bann_ctx {
   int64_t packed_bytes = 0, total_p = 0;
   // device buffers
   BranchDev* d_br = nullptr;
-  uint8_t* d_xu2 = nullptr;  // 2-bit genotype tile images of every branch (u2t, kernels_fx.hip)
+  uint8_t* d_xu2 = nullptr;  // 2-bit genotype tile images of every branch (u2t, fx_tile.h)
   uint8_t* d_xi = nullptr;   // individual-major 2-bit images of the fx branches (kernels_fi.hip; BANN_FWD_FI=0: none)
   int64_t xi_bytes = 0;
   int32_t cus = 256;

@@ -4,7 +4,7 @@
 // Both kernels are this pass up to the branch output; what a kernel does with `out`
 // is its own and lives in its file.  The pass is described here, once.
 //
-// Why.  The single-model forward (k_forward_fx, kernels_fx.hip) is bound by the
+// Why.  The single-model forward (k_forward_fx, kernels_fx_fwd.hip) is bound by the
 // genotype stream: its i8 MFMA work per tile is a fraction of the time the tile
 // takes to arrive, and a chain of K models one by one streams the same image K
 // times.  Here every 64-individual tile is streamed once per pass of KM models.
@@ -39,7 +39,7 @@
 // k_stats_fe's backward chain has expressions the compiler may contract two ways (1 - h h
 // times err); which way depends on the surrounding code.  Shared here is every piece whose
 // sharing leaves k_stats_fe's instructions exactly as they were and k_forward_fe's
-// registers, LDS-DMA sites and timing as they were: the counted wait, a digit operand,
+// registers, LDS-DMA sites and timing as they were: a digit operand,
 // the four MFMAs of (chunk, model), the head's forward and the host dispatch.  The rest
 // stays in the kernels, once each and the same text -- the lane geometry, the per-model
 // prologue, the chunk walk's skeleton and the piece-issue loop: as functions over the
@@ -57,23 +57,6 @@
 #define FE_WAVES 4
 #define FE_SLOT 8192  // one tile image at <= 8 chunks
 #define FE_NS 2       // tile slots per wave: the stream runs FE_NS tiles ahead
-
-// all but the youngest k (0 .. MAXK, MAXK = 8 or 9) vector-memory operations of this wave are complete
-template <int MAXK>
-__device__ __forceinline__ void fe_vm_wait(int k) {
-  switch (k) {
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case MAXK > 8 ? 9 : -1: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
 
 // prologue: the lane's W0 digit operand of chunk c (dg: the model's digit image of the branch + 16 lane); chunks past
 // nch are zero operands, loaded from the last real chunk so that the load needs no branch
@@ -133,15 +116,7 @@ __device__ __forceinline__ float fe_head(v4i (&facc)[4], float zscale, const flo
 // is instantiated for; other layer counts launch nothing, activations past 3 are the identity's
 template <class F>
 static void fe_dispatch(int32_t L, int32_t act, F&& f) {
-  auto with_act = [&](auto nl) {
-    switch (act) {
-      case 0: f(nl, std::integral_constant<int, 0>{}); break;
-      case 1: f(nl, std::integral_constant<int, 1>{}); break;
-      case 2: f(nl, std::integral_constant<int, 2>{}); break;
-      case 3: f(nl, std::integral_constant<int, 3>{}); break;
-      default: f(nl, std::integral_constant<int, 4>{}); break;
-    }
-  };
+  auto with_act = [&](auto nl) { act_dispatch(act, [&](auto a) { f(nl, a); }); };
   switch (L) {
     case 2: with_act(std::integral_constant<int, 2>{}); break;
     case 3: with_act(std::integral_constant<int, 3>{}); break;

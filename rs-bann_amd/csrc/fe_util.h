@@ -1,5 +1,5 @@
 // fe_util.h — the device helpers of k_forward_fx's tile arithmetic, one definition
-// for every kernel that owes its bits (kernels_fx.hip, kernels_fi.hip and, through
+// for every kernel that owes its bits (the fx family through fx_tile.h, kernels_fi.hip and, through
 // fe_stream.h, kernels_fe.hip and kernels_fs.hip): the row-sum MFMA, the digit
 // combine, the lane transpose and the pin of a wave-uniform float.
 #pragma once

@@ -106,6 +106,33 @@ __device__ __forceinline__ void glds4(const void* gsrc, const void* lds_dst) {
   const uint32_t m0 = __builtin_amdgcn_readfirstlane(lds_off(lds_dst));
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" ::"s"(m0), "v"(gsrc) : "memory", "m0");
 }
+// The counted wait on those DMAs (and on any other vector-memory operation): all but the
+// youngest k of this wave are complete.  k = MINK .. MAXK waits for exactly that; every other k
+// (0 among them) waits for all of them, which is always safe.  The bounds are the range a call
+// site can ask for: where k is not a compile-time constant the switch becomes a compare tree in
+// the tile loop, one leaf per case.  (vmcnt holds 6 bits on gfx9.)
+template <int MAXK, int MINK = 1>
+__device__ __forceinline__ void vm_wait(int k) {
+  static_assert(1 <= MINK && MINK <= MAXK && MAXK <= 31, "cases are written out for 1 .. 31");
+#define VM_WAIT_CASE(i)                                     \
+  case i:                                                   \
+    if constexpr (MINK <= i && i <= MAXK) {                 \
+      asm volatile("s_waitcnt vmcnt(" #i ")" ::: "memory"); \
+      return;                                               \
+    }                                                       \
+    break;
+  switch (k) {
+    VM_WAIT_CASE(1) VM_WAIT_CASE(2) VM_WAIT_CASE(3) VM_WAIT_CASE(4) VM_WAIT_CASE(5) VM_WAIT_CASE(6)
+    VM_WAIT_CASE(7) VM_WAIT_CASE(8) VM_WAIT_CASE(9) VM_WAIT_CASE(10) VM_WAIT_CASE(11) VM_WAIT_CASE(12)
+    VM_WAIT_CASE(13) VM_WAIT_CASE(14) VM_WAIT_CASE(15) VM_WAIT_CASE(16) VM_WAIT_CASE(17) VM_WAIT_CASE(18)
+    VM_WAIT_CASE(19) VM_WAIT_CASE(20) VM_WAIT_CASE(21) VM_WAIT_CASE(22) VM_WAIT_CASE(23) VM_WAIT_CASE(24)
+    VM_WAIT_CASE(25) VM_WAIT_CASE(26) VM_WAIT_CASE(27) VM_WAIT_CASE(28) VM_WAIT_CASE(29) VM_WAIT_CASE(30)
+    VM_WAIT_CASE(31)
+    default: break;
+  }
+#undef VM_WAIT_CASE
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
 __device__ __forceinline__ void lds_st_f32(float* p, float v) {
   asm volatile("ds_write_b32 %0, %1" ::"v"(lds_off(p)), "v"(v) : "memory");
 }

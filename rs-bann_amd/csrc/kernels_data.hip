@@ -14,7 +14,7 @@
 // streams into it through a bounded staging buffer: int8 genotypes, the .bed
 // payload (code LUT, bed_lookup_tables.rs:4) or the synthetic cohort; column
 // statistics come from the 2-bit image; and finalize packs all branches' tile
-// images (u2t layout, kernels_fx.hip) in ONE batched launch: a 64-individual
+// images (u2t layout, fx_tile.h) in ONE batched launch: a 64-individual
 // tile row of a marker is 16 bytes of its raw row, so the pack is a gather of
 // 16-byte pieces, transposed through LDS so that both the reads (128 B per
 // marker and 8 tiles) and the writes (1 KiB per chunk and tile) are contiguous.
@@ -320,7 +320,7 @@ void launch_unpack_markers(const uint8_t* raw, int64_t rowb, const int32_t* snp_
 }
 
 // ---------------------------------------------------------------------------
-// batched pack of every branch's tile image (u2t layout, kernels_fx.hip header):
+// batched pack of every branch's tile image (u2t layout, fx_tile.h):
 // tile t of marker row r of a branch = bytes [16 t, 16 t + 16) of raw row idx[r]
 // (zeros for the rows that pad m up to whole chunks).  One workgroup per
 // (chunk job, 8 tiles): 64 rows x 8 tiles of 16 B, read 128 B per row, written

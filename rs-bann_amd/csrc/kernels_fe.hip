@@ -11,6 +11,18 @@
 
 #include "fe_stream.h"
 
+// This kernel's counted wait: vm_wait<8> (kernel_util.h) plus a case that no call reaches.  The
+// switch has carried `case -1` (-> vmcnt(9)) since the wait was shared with k_stats_fe, whose ninth
+// case it stood in for.  The compiler builds its compare tree from the case set, so dropping the case
+// reorders the tree in the tile loop (about 50 instruction lines per instantiation,
+// profiles/fx_split_refactor.md): a change of this kernel's instructions, to be measured on its own.
+__device__ __forceinline__ void fe_vm_wait8(int k) {
+  if (k == -1)
+    asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+  else
+    vm_wait<8>(k);
+}
+
 // One instantiation per (layers, activation) serves every chunk count <= 8: the per-chunk guards are
 // wave-uniform scalar branches (an 8-chunk specialisation without them let the scheduler lengthen the
 // fragments' live ranges into spills of the digit operands)
@@ -100,7 +112,7 @@ __global__ void __launch_bounds__(64 * FE_WAVES, 2)
     // younger than this tile's pieces: the previous tile's stores (issued below, in front of the
     // refill) and the next tile's nch pieces, one vector-memory instruction per chunk.  Counting
     // the pieces alone is the safe side whether or not stores and loads retire in issue order
-    fe_vm_wait<8>(tt + NW < te ? nch : 0);
+    fe_vm_wait8(tt + NW < te ? nch : 0);
     store_prev();
     // the chunk walk, the same text as k_stats_fe (kernels_fs.hip): the chunk's fragments once, then every model's
     // MFMAs against them; the next chunk's LDS read is in flight meanwhile

@@ -4,7 +4,7 @@
 // individual, for the network-joint sampler's per-step forward and the
 // prediction paths.
 //
-// Why a second image.  The gradient kernel (kernels_fx.hip) needs the genotype
+// Why a second image.  The gradient kernel (kernels_fx.hip; image: fx_tile.h) needs the genotype
 // block in both orientations (forward: K = markers, backward: K = individuals)
 // and gets them from one marker-major tile image through LDS (transposing
 // ds_read_b64_tr_b8 for the forward).  A forward alone needs one orientation
@@ -246,13 +246,10 @@ template <int NL, int NSEG>
 static void launch_fi_nl(const DevState& st, const GradItem* items, int32_t nitems, int act, int grid,
                          hipStream_t s) {
   const dim3 g((unsigned)grid), block(64 * FI_WAVES);
-  switch (act) {
-    case 0: hipLaunchKernelGGL((k_forward_fi<NL, 0, NSEG>), g, block, 0, s, st, items, nitems); break;
-    case 1: hipLaunchKernelGGL((k_forward_fi<NL, 1, NSEG>), g, block, 0, s, st, items, nitems); break;
-    case 2: hipLaunchKernelGGL((k_forward_fi<NL, 2, NSEG>), g, block, 0, s, st, items, nitems); break;
-    case 3: hipLaunchKernelGGL((k_forward_fi<NL, 3, NSEG>), g, block, 0, s, st, items, nitems); break;
-    default: hipLaunchKernelGGL((k_forward_fi<NL, 4, NSEG>), g, block, 0, s, st, items, nitems); break;
-  }
+  act_dispatch(act, [&](auto a) {
+    constexpr int ACT = decltype(a)::value;
+    hipLaunchKernelGGL((k_forward_fi<NL, ACT, NSEG>), g, block, 0, s, st, items, nitems);
+  });
 }
 
 // items: one fx launch group (every branch has an fi image), tile0 = the prefix

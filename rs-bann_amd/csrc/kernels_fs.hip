@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(64 * FE_WAVES, 2)
     if (tt + j * NW < te) issue_tile(tt + j * NW, j);
   for (; tt < te; tt += NW, sl ^= 1) {
     // younger than this tile's pieces: the next tile's, nothing else (no stores, no other loads)
-    fe_vm_wait<9>(tt + NW < te ? pieces : 0);
+    vm_wait<9>(tt + NW < te ? pieces : 0);
     const float yv = has_y ? s_y[wave][sl][iota] : 0.f;  // read before the refill
     const bool live = 64 * (int64_t)tt + iota < n;  // rows past n contribute to no sum
     // the chunk walk, the same text as k_forward_fe (kernels_fe.hip): the chunk's fragments once, then every model's

@@ -151,7 +151,7 @@ __device__ __forceinline__ void blk_store_t(Blk& s, const BlkBounds& k, float* L
 }
 
 // one 1 KiB chunk image (64 marker rows x 64 individuals of one tile; u2t layout,
-// kernels_fx.hip header): thread t holds the dword at byte 4 t -- physical row
+// fx_tile.h): thread t holds the dword at byte 4 t -- physical row
 // position pos = t >> 2, i.e. logical marker row 16 w + ((P - 8 (w & 1)) & 15)
 // (w = pos >> 4, P = pos & 15), and individuals 16 dq .. 16 dq + 15 at bits 2 s,
 // dq = (t & 3) ^ (P >= 8 ? 2 : 0) (the swapped 8-byte halves).

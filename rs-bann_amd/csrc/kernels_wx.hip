@@ -66,7 +66,7 @@ __device__ __forceinline__ float comb4p(v4i d) {
   return (float)((d[0] << 7) + d[1]) + (float)((d[2] << 7) + d[3]) * 0x1p-14f;
 }
 
-// signed digits of V = rint(x 2^e), |V| < 2^27 (see kernels_fx.hip digits4_fx)
+// signed digits of V = rint(x 2^e), |V| < 2^27 (see fx_tile.h digits4_fx)
 __device__ __forceinline__ uint32_t digits4_wx(float x, int e) {
   const int V = (int)__builtin_rintf(__builtin_amdgcn_ldexpf(x, e));
   const uint32_t u = (uint32_t)V;

@@ -1,7 +1,7 @@
 """Build-time guards for the hand-counted memory waits of the fxl kernel.
 
 k_fused_grad_fxl<NL <= 3, ACT, FULL = 1> loads its W0-digit operands with inline
-asm and waits on them with hand-counted ``s_waitcnt vmcnt`` (kernels_fx.hip).  A
+asm and waits on them with hand-counted ``s_waitcnt vmcnt`` (kernels_fxl.hip).  A
 register spill of such an operand while its load is in flight would store
 garbage, so those instantiations must compile without VGPR spills.  (CPU test:
 hipcc cross-compiles gfx950 here.)"""
@@ -13,18 +13,27 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "rs-bann_amd", "csrc", "kernels_fx.hip")
+CSRC = os.path.join(ROOT, "rs-bann_amd", "csrc")
+SRC = os.path.join(CSRC, "kernels_fx.hip")
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_counted_fxl_instantiations_do_not_spill(tmp_path):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics",
-                          "-c", SRC, "-o", str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
+    # the files that hold the kernels checked below, compiled side by side
+    files = ("kernels_fxl", "kernels_fx", "kernels_fx_fwd")
+    procs = [subprocess.Popen([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics",
+                               "-c", os.path.join(CSRC, f + ".hip"), "-o", str(tmp_path / (f + ".o")),
+                               "-Rpass-analysis=kernel-resource-usage"],
+                              stdout=subprocess.DEVNULL, stderr=open(tmp_path / (f + ".err"), "w")) for f in files]
+    stderr = ""
+    for f, p in zip(files, procs):
+        rc = p.wait(timeout=600)
+        err = open(tmp_path / (f + ".err")).read()
+        assert rc == 0, err[-2000:]
+        stderr += err
     spills, name = {}, None
-    for line in out.stderr.splitlines():
+    for line in stderr.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             name = m.group(1)
@@ -39,9 +48,11 @@ def test_counted_fxl_instantiations_do_not_spill(tmp_path):
     assert len(resident) == 20, resident
     assert all(spills[k] == 0 for k in resident), {k: spills[k] for k in resident}
     fx = [k for k in spills if k.startswith("_Z15k_fused_grad_fx")]
-    assert fx and all(spills[k] == 0 for k in fx), {k: spills[k] for k in fx}
+    assert len(fx) == 60, len(fx)  # (a lost instantiation must not pass as "all of none")
+    assert all(spills[k] == 0 for k in fx), {k: spills[k] for k in fx}
     fwd = [k for k in spills if k.startswith("_Z12k_forward_fx")]
-    assert fwd and all(spills[k] == 0 for k in fwd), {k: spills[k] for k in fwd}
+    assert len(fwd) == 30, len(fwd)
+    assert all(spills[k] == 0 for k in fwd), {k: spills[k] for k in fwd}
 
 
 def test_production_build_sets_no_profiling_switches():
@@ -51,6 +62,22 @@ def test_production_build_sets_no_profiling_switches():
     txt = open(SRC).read()
     for sw in ("FX_STAMPS", "FX_ABL"):
         assert f"#ifndef {sw}\n#define {sw} 0\n#endif" in txt, sw
-    mk = open(os.path.join(os.path.dirname(SRC), "Makefile")).read()
+    mk = open(os.path.join(CSRC, "Makefile")).read()
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert "-DFX_" not in mk and "-DFX_" not in entry and "BANN_ABLATE" not in mk
+
+
+def test_makefile_srcs_is_the_only_source_list():
+    """every HIP source of the library is in the Makefile's SRCS, and tools/build_ab.sh takes its
+    list from there (print-srcs) instead of carrying one that can drift"""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    srcs = re.search(r"^SRCS = (.*)$", mk, re.M).group(1).split()
+    on_disk = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    assert sorted(srcs) == on_disk
+    assert len(set(srcs)) == len(srcs)
+    assert re.search(r"^print-srcs:", mk, re.M)
+    ab = open(os.path.join(ROOT, "tools", "build_ab.sh")).read()
+    assert "print-srcs" in ab
+    names = [s[:-4] for s in srcs]
+    for line in [l for l in mk.splitlines() if not l.startswith("SRCS = ")] + ab.splitlines():
+        assert sum(1 for w in re.findall(r"\w+", line) if w in names) <= 1, line

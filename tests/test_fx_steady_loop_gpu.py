@@ -1,4 +1,4 @@
-"""The fx gradient kernel's two tile loops (kernels_fx.hip, FX_STEADY): a steady body for
+"""The fx gradient kernel's two tile loops (k_fused_grad_fx, kernels_fx.hip): a steady body for
 tiles whose successor two rounds on exists and is full, the guarded body for the rest.
 
 Shapes are chosen by how many steady iterations a wave of a ONE-item branch runs (the

@@ -1,13 +1,14 @@
 #!/bin/bash
 # variant library for A/B runs: tools/build_ab.sh <tag> "<extra hipcc flags>" [files]
 #   -> rs-bann_amd/ab/librsbann_amd_<tag>.so
-# files (default: every .hip source) are compiled with the flags; the other objects are
-# taken from the in-tree build (make -C rs-bann_amd/csrc first)
-# e.g. the fx tile loop without its steady body: tools/build_ab.sh steady0 "-DFX_STEADY=0" kernels_fx
+# files (default: every .hip source; the Makefile's SRCS is the list) are compiled with the flags;
+# the other objects are taken from the in-tree build (make -C rs-bann_amd/csrc first)
+# e.g. the fx gradient with its phase stamps: tools/build_ab.sh stamps "-DFX_STAMPS=1" kernels_fx
 set -e
-ALL="bann_api bann_dist bann_residual bann_io_dev kernels_data kernels_gx kernels_fx kernels_wx kernels_update kernels_feed kernels_fi kernels_fe kernels_fs kernels_gibbs kernels_init kernels_ld bann_ld"
+R=$(cd "$(dirname "$0")/.." && pwd); C=$R/rs-bann_amd/csrc
+ALL=$(make -s --no-print-directory -C $C print-srcs)
 TAG=$1; FLAGS=$2; FILES=${3:-$ALL}
-R=$(cd "$(dirname "$0")/.." && pwd); C=$R/rs-bann_amd/csrc; O=/tmp/ab_$TAG; rm -rf $O; mkdir -p $O $R/rs-bann_amd/ab
+O=/tmp/ab_$TAG; rm -rf $O; mkdir -p $O $R/rs-bann_amd/ab
 for f in $FILES; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result -munsafe-fp-atomics $FLAGS -c $C/$f.hip -o $O/$f.o 2>/dev/null &
 done

@@ -1,7 +1,10 @@
 """Instruction counts of a kernel's hot loop from hipcc assembly (-S).
 
-    hipcc -O3 --offload-arch=gfx950 --offload-device-only -S -o k.s kernels_fx.hip
+    hipcc -O3 --offload-arch=gfx950 --offload-device-only -S -o k.s <the file that holds the kernel>
     python tools/isa_count.py k.s <symbol substring> [--block-exclude LABEL ...]
+
+(k_fused_grad_fx: kernels_fx.hip, k_forward_fx: kernels_fx_fwd.hip, k_forward_gsum: kernels_fx_gsum.hip,
+k_fused_grad_fxl: kernels_fxl.hip, k_fused_grad_fxh: kernels_fxh.hip)
 
 Finds the kernel, its basic blocks, and the outermost backward branch whose body
 holds MFMAs (the tile loop); prints per-block and whole-loop counts by class
