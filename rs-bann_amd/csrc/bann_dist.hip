@@ -23,10 +23,20 @@
 
 #include "ctx_internal.h"
 
-void comm_destroy(bann_ctx* ctx) {
+static void comm_destroy(bann_ctx* ctx) {
   if (ctx->nccl) (void)ncclCommDestroy((ncclComm_t)ctx->nccl);
   ctx->nccl = nullptr;
   ctx->comm_kind = 0;
+}
+
+// the communicator, net_buffers_init's buffers and the all-reduce's f64 staging
+void dist_release(bann_ctx* ctx) {
+  comm_destroy(ctx);
+  dfree_all(ctx->d_netsum, ctx->d_nety, ctx->d_netrss, ctx->d_netpart, ctx->d_ar64, ctx->d_gsum, ctx->d_ones, ctx->d_cm,
+            ctx->d_cm_scale);
+  ctx->netrss_cap = ctx->gsum_cap = 0;
+  ctx->ar64_cap = 0;
+  ctx->cm_have_scale = false;
 }
 
 extern "C" int bann_shard_branches(const int32_t* marker_counts, int32_t nbranches, int32_t world,

@@ -1,5 +1,5 @@
 // bann_internal.h — device-visible descriptors and launcher declarations shared
-// by the HIP kernels (kernels_*.hip) and the C-ABI implementation (bann_api.hip).
+// by the HIP kernels (kernels_*.hip) and the C-ABI implementation (bann_*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -30,7 +30,7 @@
 // bann_residual.hip (library-internal): bann_residual_from_target + bann_residual_shift(add) in one launch
 int residual_from_target_shift(bann_ctx* ctx, int32_t b, float add, double* sum, double* sumsq, double* sum_after,
                                double* sumsq_after);
-// bann_api.hip (library-internal): bann_hmc_step + bann_branch_get_params + residual_from_target_shift
+// bann_hmc.hip (library-internal): bann_hmc_step + bann_branch_get_params + residual_from_target_shift
 // for one branch with one host wait (stats: sum, sum of squares before / after the shift)
 int hmc_step_tail(bann_ctx* ctx, int32_t b, int32_t L, float max_dh, int32_t step_mode, float factor, const float* eps,
                   const float* momentum, uint64_t seed, const float* u, float add, int32_t* status_out,

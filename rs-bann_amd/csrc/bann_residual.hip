@@ -176,6 +176,12 @@ static int ensure_residual(bann_ctx* ctx) {
   return BANN_OK;
 }
 
+void residual_release(bann_ctx* ctx) {
+  dfree_all(ctx->d_res, ctx->d_res_part);
+  if (ctx->h_res_stat) (void)hipHostFree(ctx->h_res_stat);
+  ctx->h_res_stat = ctx->d_res_stat_host = nullptr;
+}
+
 // predictions of the listed branches current (pred_b = f_b(theta_b)): one packed
 // launch over the branches whose prediction row is stale
 int ensure_predictions(bann_ctx* ctx, const int32_t* branches, int32_t nb) {

@@ -1,5 +1,6 @@
 // ctx_internal.h — the bann_ctx context and the host helpers shared by the C-ABI
-// translation units (bann_api.hip: single-GPU API; bann_dist.hip: multi-GPU).
+// translation units (bann_ctx / plan / genotypes / branch / eval / hmc / models .hip: the
+// single-GPU API, one file per concern; bann_dist.hip: multi-GPU).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -274,54 +275,110 @@ inline void dfree(void* p) {
   if (p) (void)hipFree(p);
 }
 
-// implemented in bann_api.hip
+// free and null device buffers (the *_release functions)
+template <typename... T>
+inline void dfree_all(T*&... p) {
+  (dfree(p), ...);
+  ((p = nullptr), ...);
+}
+
+// What crosses a file boundary, under the file that implements it.  bann_ctx_destroy calls the
+// *_release functions: each frees and nulls exactly what its file allocates, after waiting
+// for a pending event whose pinned stage it frees.
+
+// ---- bann_ctx.hip ----
 void refresh_state(bann_ctx* ctx);
 bool check_branch(const bann_ctx* ctx, int32_t b);
+
+// ---- bann_plan.hip ----
+int plan_scratch_alloc(bann_ctx* ctx, const LayoutTotals& t);  // bann_finalize: the scratch of per-call plans
+void plan_release(bann_ctx* ctx);
 int build_plan(bann_ctx* ctx, const int32_t* branches, int32_t nb, Plan& p, bool persistent);
 void free_plan(Plan& p);
+// one fused group's gradient launch, and the plan's gx phases, on a state of the caller's (the model slots')
+void launch_group_grad(const bann_ctx* ctx, const DevState& s, const LaunchGroup& g, int wp, int upd_mode,
+                       int upd_step, int32_t* cnt, const FoldJob* fo);
+void launch_gx_phases(const bann_ctx* ctx, const DevState& s, const Plan& p, bool head_only);
 int run_grad(bann_ctx* ctx, const Plan& p, int write_pred, int upd_mode = -1, int upd_step = 0);
 int run_forward(bann_ctx* ctx, const Plan& p);  // predictions only
 void run_update(bann_ctx* ctx, const Plan& p, int32_t mode, int32_t step);
-int ensure_htrace(bann_ctx* ctx, int32_t L);
+void mark_predictions(bann_ctx* ctx, const Plan& p, bool current);
+
+// ---- bann_genotypes.hip ----
 int alloc_genotypes(bann_ctx* ctx, int64_t n, int64_t M);   // the 2-bit genotype image of n x M
+void genotypes_release(bann_ctx* ctx);
 int64_t stage_markers(int64_t bytes_per_marker, int64_t M);  // markers per ~256 MiB staging block
 // keep_missing, around a .bed load: allocate the presence image after alloc_genotypes (nothing with keep
 // off); after the last launch_bed_to_presence count the missing calls and drop the image if there is none
 int alloc_presence(bann_ctx* ctx);
 int finish_presence(bann_ctx* ctx);
-int ensure_predictions(bann_ctx* ctx, const int32_t* branches, int32_t nb);  // bann_residual.hip
-void launch_residual_sub(float* r, const float* d, int64_t n, hipStream_t s);
-void mark_predictions(bann_ctx* ctx, const Plan& p, bool current);
+
+// ---- bann_branch.hip ----
+void branch_release(bann_ctx* ctx);  // bann_finalize's state and upload_precisions' stage
+// expanded per-parameter precision multipliers and the error precision of the host precision vector
+void expand_precisions(const BranchHost& h, std::vector<float>& lam, std::vector<float>& lamld, float& eprec);
+int upload_precisions(bann_ctx* ctx, int32_t b);  // branch b's precision-derived device arrays, no host wait
+
+// ---- bann_eval.hip ----
+// device scratch of the effect-size chain, sized for the largest listed branch
+struct EffectScratch {
+  float *pre = nullptr, *act = nullptr, *ea = nullptr, *eb = nullptr, *full = nullptr, *pop = nullptr;
+  double* s = nullptr;
+  ~EffectScratch();
+  hipError_t alloc(const bann_ctx* ctx, const int32_t* branches, int32_t nb, bool want_full);
+};
+
+// ---- bann_hmc.hip ----
+void hmc_release(bann_ctx* ctx);
+void clear_graphs(bann_ctx* ctx);
+int ensure_htrace(bann_ctx* ctx, int32_t L);
 int traj_prepare(bann_ctx* ctx, const Plan& p, int32_t L, float max_dh, int32_t step_mode, float factor,
                  const float* eps, const float* momentum, uint64_t seed, const float* u);
+// the sequential driver's branch-update tail (for bann_net.cpp)
+int hmc_step_tail(bann_ctx* ctx, int32_t b, int32_t L, float max_dh, int32_t step_mode, float factor, const float* eps,
+                  const float* momentum, uint64_t seed, const float* u, float add, int32_t* status_out,
+                  float* params_out, double* stats);
 // in-trajectory launch timing (bann_set_launch_timing): event marks on the context stream
 enum { TM_GRAD0 = 0, TM_GRAD1 = 1, TM_UPD1 = 2, TM_AR0 = 3, TM_AR1 = 4, TM_FWD0 = 5, TM_FWD1 = 6 };
 void tm_mark(bann_ctx* ctx, int32_t kind);
 void tm_mark_follow(bann_ctx* ctx, int32_t kind);
 int tm_resolve(bann_ctx* ctx);  // after the stream has drained
-// bann_dist.hip: the network sampler's device buffers, allocated once at bann_finalize
-// (no allocation or synchronous upload inside a collective trajectory)
-// the sequential driver's branch-update tail (bann_api.hip / bann_residual.hip)
+
+// ---- bann_models.hip ----
+void models_release(bann_ctx* ctx);
+
+// ---- bann_residual.hip ----
+void residual_release(bann_ctx* ctx);
+int ensure_predictions(bann_ctx* ctx, const int32_t* branches, int32_t nb);
+void launch_residual_sub(float* r, const float* d, int64_t n, hipStream_t s);
 int residual_from_target_shift(bann_ctx* ctx, int32_t b, float add, double* sum, double* sumsq, double* sum_after,
                                double* sumsq_after);
 int residual_from_target_shift_launch(bann_ctx* ctx, int32_t b, float add);
-int hmc_step_tail(bann_ctx* ctx, int32_t b, int32_t L, float max_dh, int32_t step_mode, float factor, const float* eps,
-                  const float* momentum, uint64_t seed, const float* u, float add, int32_t* status_out,
-                  float* params_out, double* stats);
-// kernels_init.hip (library-internal, for bann_net.cpp): bann_init_branches over every branch with the
+
+// ---- kernels_gibbs.hip ----
+void gibbs_release(bann_ctx* ctx);
+
+// ---- kernels_init.hip ----
+void init_release(bann_ctx* ctx);
+// (library-internal, for bann_net.cpp): bann_init_branches over every branch with the
 // joint output-layer precision nb / sum_b sum w_out,b^2 in every branch's output-layer entry (the fixed
 // precision when there is one); reg_sum_out = sum_b summary_stat_fn(w_out,b), branch order, f64
 int init_branches_net(bann_ctx* ctx, const bann_init_cfg* cfg, uint64_t seed, double* reg_sum_out);
 // g = (0 + bias) + sum_b f_b in branch order (f32) at the context's parameters, y = g + noise, the
 // moments; bann_net_simulate_y without the net (include/bann_net.h)
 int simulate_y_device(bann_ctx* ctx, float bias, float heritability, uint64_t seed, float* y_out, float stats_out[3]);
-// kernels_init.hip, for kernels_lin.hip: simulate-y's moment and noise launches on a vector of the caller's.
+// for kernels_lin.hip: simulate-y's moment and noise launches on a vector of the caller's.
 // part: sim_moment_blocks(n) doubles of scratch; sums[0] = sum x, sums[1] = sum (x - mean)^2; no host wait
 int64_t sim_moment_blocks(int64_t n);
 void sim_launch_moments(const float* x, int64_t n, double* part, double* sums, hipStream_t s);
 // y_i += (float)(sqrt(rv) z_i), rv = ss[0] / (n - 1) * inv_h_m1 also to *rv_out, z_i of stream (seed, NOISE)
 void sim_launch_noise(float* y, int64_t n, double inv_h_m1, const double* ss, uint64_t seed, double* rv_out,
                       hipStream_t s);
+
+// ---- bann_dist.hip ----
+void dist_release(bann_ctx* ctx);  // the communicator and the network sampler's buffers
+// the network sampler's device buffers, allocated once at bann_finalize (no allocation or
+// synchronous upload inside a collective trajectory)
 int net_buffers_init(bann_ctx* ctx);
 // network mode: k_forward_gsum's items for a persistent fx-only plan of 8-chunk branches
 int build_net_groups(bann_ctx* ctx, Plan& p);

@@ -87,7 +87,7 @@ constexpr int FXT_PD_EDGE = 4;
 // NCH: 8 = every branch of the launch has exactly 8 chunks (no per-chunk guards,
 // so the LDS reads of a whole phase issue back to back); 0 = any count <= 8.
 
-// UPD: the instantiation with the fused update tail (bann_api.hip fuse_update plans);
+// UPD: the instantiation with the fused update tail (bann_plan.hip fuse_update plans);
 // the default one carries no tail code at all (its registers: the tail's live values
 // made the tile loop spill scalar registers to vector lanes)
 template <int NL, int ACT, int NCH, int UPD>
@@ -631,7 +631,7 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
       st.rss_part[it.rss_at] = rs;
   }
   if constexpr (UPD) {
-    // fused leapfrog update (bann_api.hip build_plan): the last of the branch's
+    // fused leapfrog update (bann_plan.hip build_plan): the last of the branch's
     // workgroups to finish updates it here, with the update kernel's arithmetic and
     // reduction order (update_small as 512 virtual threads), instead of a second
     // launch -- after folding the branch's slabs first in a solo plan (folds: the

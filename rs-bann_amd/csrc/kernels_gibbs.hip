@@ -205,6 +205,10 @@ int gibbs_stats(bann_ctx* ctx, const int32_t* branches, int32_t nb, const float*
 
 }  // namespace
 
+void gibbs_release(bann_ctx* ctx) {  // gibbs_buffers'
+  dfree_all(ctx->d_gb_shape, ctx->d_gb_scale, ctx->d_gb_prec, ctx->d_gb_out, ctx->d_gb_list);
+}
+
 extern "C" int bann_gibbs_posterior(bann_ctx* ctx, const int32_t* branches, int32_t nb, const float* hyper,
                                     double* shape_out, double* scale_out, double* out_stat_out) {
   int rc = gibbs_check(ctx, branches, nb, hyper);

@@ -356,6 +356,10 @@ void launch_moments(bann_ctx* ctx, const float* x, double* sums) {
 
 }  // namespace
 
+void init_release(bann_ctx* ctx) {  // init_buffers' and simulate-y's partials
+  dfree_all(ctx->d_init_prec, ctx->d_init_stat, ctx->d_init_list, ctx->d_sim_part);
+}
+
 int64_t sim_moment_blocks(int64_t n) { return sim_blocks(n); }
 
 void sim_launch_moments(const float* x, int64_t n, double* part, double* sums, hipStream_t s) {

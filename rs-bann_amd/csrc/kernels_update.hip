@@ -589,7 +589,7 @@ void launch_snapshot_pred(const DevState& st, const int32_t* branches, int32_t n
 }
 
 // step sizes on the device (uniform 706-732; izmailov: see step_bases in
-// bann_api.hip): eps = c, or |base| * (base > 0 ? c : 1) / L, rounded once to f32
+// bann_branch.hip): eps = c, or |base| * (base > 0 ? c : 1) / L, rounded once to f32
 __global__ void __launch_bounds__(256) k_step_sizes(DevState st, const double* __restrict__ base,
                                                     const int32_t* __restrict__ blist, int izmailov, float c, int L) {
   const int b = blist[blockIdx.y];

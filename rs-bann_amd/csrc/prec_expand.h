@@ -1,6 +1,6 @@
 // prec_expand.h — what bann_branch_set_precisions derives from a precision vector, on the
 // device: the per-parameter prior multipliers lam / lamld and the Izmailov step bases
-// (expand_precisions and step_bases of bann_api.hip).  Shared by the Gibbs draw
+// (expand_precisions and step_bases of bann_branch.hip).  Shared by the Gibbs draw
 // (kernels_gibbs.hip) and the model initialisation (kernels_init.hip).
 #pragma once
 #include <hip/hip_runtime.h>

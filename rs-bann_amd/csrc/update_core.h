@@ -117,7 +117,7 @@ __device__ void block_sum_nv(double (&v)[R][NV], double* red) {
 }
 
 // R > 1: NT real threads play a workgroup of NT * R (the fused update in the tail
-// of the fx gradient launch, bann_api.hip run_grad): every per-element operation,
+// of the fx gradient launch, bann_plan.hip run_grad): every per-element operation,
 // every partial sum and both reductions in the order of update_small<NT * R>.
 template <int NT, int MPT, int R = 1>
 __device__ void update_small(const DevState& st, int b, const BranchDev& bd, int mode, bool prof, int step,

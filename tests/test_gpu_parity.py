@@ -104,7 +104,7 @@ CONFIGS = [
 
 
 def expected_path(cfg, fused):
-    """the kernel family bann_finalize picks (bann_api.hip)"""
+    """the kernel family bann_finalize picks (bann_branch.hip, plan_layout of finalize_layout.h)"""
     w, m = cfg["widths"], cfg["m"]
     if not fused:
         return "layered"
@@ -1183,7 +1183,7 @@ def test_fused_update_session_bitwise(Ctx, monkeypatch, shape, fused):
             monkeypatch.delenv("BANN_FUSE_UPDATE", raising=False)
         else:
             monkeypatch.setenv("BANN_FUSE_UPDATE", fuse)
-        ctx = build_context(Ctx, g, specs)   # single: 600 branches -> 1 split each (bann_api.hip best_splits)
+        ctx = build_context(Ctx, g, specs)   # single: 600 branches -> 1 split each (finalize_layout.h best_splits)
         res = []
         for traj, (L, f) in enumerate([(5, 0.05), (3, 2.0), (8, 0.02)]):
             ctx.leapfrog_begin(list(range(nb)), L, 10.0, "izmailov", f, seed=3 + traj)
