@@ -77,22 +77,19 @@ __device__ __forceinline__ void fe_mfma4(v4i a, v4i f0, v4i f1, v4i f2, v4i f3, 
 // lane) -> f.  Every layer's pre-activation z[l] and activation a[l] is left to the caller (k_stats_fe's
 // backward chain; dead in k_forward_fe); widths below 4 are zero-padded, so padded units carry exact zeros
 template <int NL, int ACT>
-__device__ __forceinline__ float fe_head(v4i (&facc)[4], float zscale, const float (*hw)[20], float (&z)[NL - 1][4],
+__device__ __forceinline__ float fe_head(v4i (&facc)[4], float zk, const float (*hw)[20], float (&z)[NL - 1][4],
                                          float (&a)[NL - 1][4]) {
   constexpr int NH = NL - 1;
-  facc[3] -= facc[2];
-  facc[2] -= facc[1];
-  facc[1] -= facc[0];
-  float z0 = zscale * comb4(facc[0]), z1 = (0.25f * zscale) * comb4(facc[1]);
-  float z2 = (0.0625f * zscale) * comb4(facc[2]), z3 = (0.015625f * zscale) * comb4(facc[3]);
+  float z0, z1, z2, z3;  // with the first-layer bias: the lane's column (lane >> 4) before the transpose
+  fx_z0_cum(facc, zk, hw[0][16 + ((threadIdx.x >> 4) & 3)], z0, z1, z2, z3);
   swap32(z0, z2);
   swap32(z1, z3);
   swap16(z0, z1);
   swap16(z2, z3);
-  z[0][0] = z0 + hw[0][16];
-  z[0][1] = z1 + hw[0][17];
-  z[0][2] = z2 + hw[0][18];
-  z[0][3] = z3 + hw[0][19];
+  z[0][0] = z0;
+  z[0][1] = z1;
+  z[0][2] = z2;
+  z[0][3] = z3;
 #pragma unroll
   for (int k = 0; k < 4; ++k) a[0][k] = act_h_t<ACT>(z[0][k]);
 #pragma unroll

@@ -32,8 +32,12 @@ constexpr int FXL_PD = 8;  // fxl, fxh: the backward reads its genotype windows 
 // the 2-bit field holds -1 .. 1).  The forward takes CUMULATIVE fragments -- x & 0x03, x & 0x0F,
 // x & 0x3F and the raw byte: 3 ANDs per dword instead of 5 -- and recovers the in-place fields
 // exactly in int32 once per tile: F1 = C1 - C0, F2 = C2 - C1, F3 = C3 - C2 with C3 started at
-// 64 sum_k A (the W0-digit row sums over the wave's chunks, rowsum64_acc), so F_q = 4^q S_q as
-// before and z keeps its bits.  The backward keeps field 3 in place too (x & 0xC0 = 64 (f3 - 1):
+// 64 sum_k A (the W0-digit row sums over the wave's chunks, rowsum64_acc), so F_q = 4^q S_q.  With
+// at most 8 chunks the four digits of a fragment are first combined in pairs in int32, the
+// differences are taken on the pairs and Z0 comes out of one fma per pair of pairs with the bias as
+// its addend (fx_z0_cum, fe_util.h; the arithmetic and its bounds: fx_combine.h); the wide items
+// of fxl / fxh take the differences per digit (fx_fwd_fields) and the four-digit combine (comb4).
+// The backward keeps field 3 in place too (x & 0xC0 = 64 (f3 - 1):
 // one AND instead of a shift and an AND), with the delta0 digits of K-group 3 pre-divided by 64;
 // the -1 comes back as 64 sum_(i in group 3) digit_i, one MFMA per tile against FX_ONES3, added
 // to every marker's digit sums at the end.
@@ -47,7 +51,8 @@ __device__ __forceinline__ void fx_fwd_chunk(v4i A, v4u X, v4i (&facc)[4]) {
   facc[2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, (v4i)(X & 0x3F3F3F3Fu), facc[2], 0, 0, 0);
   facc[3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, (v4i)X, facc[3], 0, 0, 0);
 }
-// cumulative sums -> in-place fields F_q = 4^q S_q (facc[3] started at the rowsum64_acc sum)
+// cumulative sums -> in-place fields F_q = 4^q S_q (facc[3] started at the rowsum64_acc sum), digit by
+// digit: fxl and fxh, whose items are wider than the pair combine's 8 chunks
 __device__ __forceinline__ void fx_fwd_fields(v4i (&facc)[4]) {
   facc[3] -= facc[2];
   facc[2] -= facc[1];

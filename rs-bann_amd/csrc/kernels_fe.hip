@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(64 * FE_WAVES, 2)
   // per model: head parameters and 64 x the digit row sums -> LDS, W0 digit operands and the lane's column
   // scale -> registers.  The same text as k_stats_fe (kernels_fs.hip): why not a function, fe_stream.h
   v4i A[KM][8];
-  float zscale[KM];
+  float zk[KM];
 #pragma unroll
   for (int k = 0; k < KM; ++k) {
     if (threadIdx.x < NL * 20) {
@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(64 * FE_WAVES, 2)
       }
       s_hw[k][l][r] = v;
     }
-    zscale[k] = mm.fc[k][b].scale[lane >> 4];
+    zk[k] = fx_zk(mm.fc[k][b].scale[lane >> 4]);
     v4i rowsum64 = v4i{0, 0, 0, 0};
     const uint8_t* dg = mm.dig[k] + bd.dig_off + lane * 16;
 #pragma unroll
@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(64 * FE_WAVES, 2)
     for (int k = 0; k < KM; ++k) {
       if (k < nk) {
         float z[NL - 1][4], a[NL - 1][4];
-        obuf[k] = fe_head<NL, ACT>(facc[k], zscale[k], s_hw[k], z, a);
+        obuf[k] = fe_head<NL, ACT>(facc[k], zk[k], s_hw[k], z, a);
       }
       asm volatile("" ::: "memory");  // one model's head parameters at a time
     }

@@ -48,7 +48,8 @@ __device__ __forceinline__ int32_t fi_tiles(const GradItem& it) { return ((it.fr
 template <int NL>
 struct FiBranch {  // the constants of the branch a wave is streaming
   v4i A[FI_MAXSEG][4];
-  float zs;           // W0/sigma digit scale of this lane's column, / 16 (the field weights)
+  float zs;           // fx_zk of the W0/sigma digit scale of this lane's column, / 16 (the field weights)
+  float b0;           // c0 of this lane's column (fxc_z0's addend)
   float W[NL][4][4];  // head weights W_l[j][k], l >= 1 (wave-uniform)
   float B[NL][4];     // c0 (l = 0), b_l
   int nseg;
@@ -85,7 +86,8 @@ __device__ __forceinline__ void fi_load_branch(const DevState& st, int b, int la
       c.A[s][p] = a;
     }
   }
-  c.zs = st.fc[b].scale[g] * 0.0625f;
+  c.zs = fx_zk(st.fc[b].scale[g]) * 0.0625f;
+  c.b0 = g < bd.widths[0] ? st.fc[b].c0[g] : 0.f;
   const float* th = st.theta + bd.p_off;
 #pragma unroll
   for (int l = 0; l < NL; ++l) {
@@ -140,7 +142,9 @@ __device__ __forceinline__ void fi_tile(const FiBranch<NL>& c, const v4u (&X)[4]
     }
     // value x 16 = 16 acc0 + 4 acc1 + acc2 + acc3, per digit, exact in int32
     const v4i D = acc[0] * 16 + acc[1] * 4 + acc[2] + acc[3];
-    z[f] = c.zs * comb4(D);  // lane (g, i): column g of individual 16 f + i
+    // lane (g, i): column g of individual 16 f + i, with its bias -- the pair combine of the fx
+    // forward (fx_combine.h), whose bits these are: a pair is 16 P, |P| <= FXC_PAIR_EXACT_MAX < 2^24
+    z[f] = fxc_z0(fxc_pair(D[0], D[1]), fxc_pair(D[2], D[3]), 1.f, c.zs, c.b0);
   }
   // transpose (frag, lane group) -> (column, lane group): lane L = individual L of the tile
   swap32(z[0], z[2]);
@@ -149,7 +153,7 @@ __device__ __forceinline__ void fi_tile(const FiBranch<NL>& c, const v4u (&X)[4]
   swap16(z[2], z[3]);
   float a[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) a[k] = act_h_t<ACT>(z[k] + c.B[0][k]);
+  for (int k = 0; k < 4; ++k) a[k] = act_h_t<ACT>(z[k]);
 #pragma unroll
   for (int l = 1; l < NH; ++l) {
     float an[4];

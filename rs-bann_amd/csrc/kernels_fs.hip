@@ -37,10 +37,10 @@
 
 // the head of one model's tile (fe_head), then the effect-size chain on its kept layers down to delta0
 template <int NL, int ACT>
-__device__ __forceinline__ float fs_head(v4i (&facc)[4], float zscale, const float (*hw)[20], float (&d0)[4]) {
+__device__ __forceinline__ float fs_head(v4i (&facc)[4], float zk, const float (*hw)[20], float (&d0)[4]) {
   constexpr int NH = NL - 1;
   float z[NH][4], a[NH][4];
-  const float out = fe_head<NL, ACT>(facc, zscale, hw, z, a);
+  const float out = fe_head<NL, ACT>(facc, zk, hw, z, a);
   float err[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) err[k] = out * hw[NL - 1][4 * k];
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(64 * FE_WAVES, 2)
   // per model: head parameters and 64 x the digit row sums -> LDS, W0 digit operands and the lane's column
   // scale -> registers.  The same text as k_forward_fe (kernels_fe.hip): why not a function, fe_stream.h
   v4i A[KM][8];
-  float zscale[KM];
+  float zk[KM];
 #pragma unroll
   for (int k = 0; k < KM; ++k) {
     if (threadIdx.x < NL * 20) {
@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(64 * FE_WAVES, 2)
       }
       s_hw[k][l][r] = v;
     }
-    zscale[k] = mm.fc[k][b].scale[lane >> 4];
+    zk[k] = fx_zk(mm.fc[k][b].scale[lane >> 4]);
     v4i rowsum64 = v4i{0, 0, 0, 0};
     const uint8_t* dg = mm.dig[k] + bd.dig_off + lane * 16;
 #pragma unroll
@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(64 * FE_WAVES, 2)
     for (int k = 0; k < KM; ++k) {
       if (k < nk) {
         float d0[4];
-        const float out = fs_head<NL, ACT>(facc[k], zscale[k], s_hw[k], d0);
+        const float out = fs_head<NL, ACT>(facc[k], zk[k], s_hw[k], d0);
         const float e = out - yv;
         acc[k][0] += (double)(live && has_y ? e * e : 0.f);
 #pragma unroll

@@ -59,7 +59,8 @@ constexpr int FXT_PD_EDGE = 4;
 // A steady tile's refill takes two 64-bit bases per tile and each piece as the instruction's immediate
 // offset, which gfx950 adds to the LDS address too (bann_fx_dma_offset_probe), so M0 is written once
 // per 4 KiB half slot; without it the two bodies spill vector registers.  The delta0 scale's two
-// fallback forms (unset -> 5 / 255) live in registers (Rg, Rd), updated only in the rare rescale path.
+// fallback forms (unset -> 5 / 255) live in registers (Rg, Rd), with Rg's threshold as a float (Tg: the
+// growth test is one float compare per column), updated only in the rare rescale path.
 // Measurements: DESIGN.md 4.
 #if FX_STAMPS
 #define FX_STAMP(i)                                            \
@@ -215,15 +216,17 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
     }
     s_hw[l][r] = v;
   }
-  float zscale = st.fc[b].scale[g];
+  float zk = fx_zk(st.fc[b].scale[g]);
   for (int c = wave; c < nch; c += NW)  // W0 digit image -> LDS (shared by the four waves)
     *reinterpret_cast<v4i*>(&s_w0[c * 1024 + lane * 16]) =
         *reinterpret_cast<const v4i*>(st.dig + bd.dig_off + ((int64_t)c * 64 + lane) * 16);
   // retire the prologue loads and hide their provenance: inside the tile loop the
   // only vector-memory waits are the explicit, counted ones on this wave's DMAs
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("" : "+v"(zscale));
+  asm volatile("" : "+v"(zk));
   __syncthreads();
+  float zbias = s_hw[0][16 + g];  // the lane's column bias c0: the addend of Z0's last fma (fx_z0_cum)
+  asm volatile("" : "+v"(zbias));
   v4i rowsum64 = v4i{0, 0, 0, 0};  // the forward's facc[3] start (field 3 stored as code - 1)
   for (int c = 0; c < nch; ++c) rowsum64 = rowsum64_acc(*reinterpret_cast<const v4i*>(&s_w0[c * 1024 + lane * 16]), rowsum64);
   // head weights as wave-uniform values: scalar registers for the whole item (the
@@ -238,9 +241,8 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
         uW[l][j][k] = (l >= 1 && (l < NL - 1 || k == 0)) ? sgpr_f(s_hw[l][4 * j + k]) : 0.f;
     if (l < NH)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) uB[l][k] = sgpr_f(s_hw[l][16 + k]);
+      for (int k = 0; k < 4; ++k) uB[l][k] = l >= 1 ? sgpr_f(s_hw[l][16 + k]) : 0.f;  // (b_0: zbias)
   }
-
 
   // ---- accumulators ----
   v4i acc[32];  // dW0 digit sums per 16-marker window u (lane: column g, marker 16u + i16)
@@ -268,6 +270,8 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
   unsigned long long t_last = mt0;
 #endif
   int Rg[4] = {5, 5, 5, 5};          // R[k] ? R[k] : 5, the growth test's threshold
+  // the same threshold as a float, 2^(Rg - 126): exponent field > Rg <=> |delta| >= it (unset: 2^-121)
+  float Tg[4] = {fpow2(6), fpow2(6), fpow2(6), fpow2(6)};
   int Rd[4] = {255, 255, 255, 255};  // R[k] ? R[k] : 255, the digit exponent's
   // one tile; ST: the steady instantiation, whose guards are compile-time true / false
   auto tile = [&](auto steady_c) __attribute__((always_inline)) {
@@ -338,9 +342,8 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
     __builtin_amdgcn_s_setprio(1);
     // lane (column g, slot i16) holds individual 4 i16 + q in register q; transpose
     // so that lane L holds all four columns of individual 4 (L & 15) + (L >> 4)
-    fx_fwd_fields(facc);  // F_q = 4^q S_q, exact
-    float z0 = zscale * comb4(facc[0]), z1 = (0.25f * zscale) * comb4(facc[1]);
-    float z2 = (0.0625f * zscale) * comb4(facc[2]), z3 = (0.015625f * zscale) * comb4(facc[3]);
+    float z0, z1, z2, z3;  // with the first-layer bias
+    fx_z0_cum(facc, zk, zbias, z0, z1, z2, z3);
     swap32(z0, z2);
     swap32(z1, z3);
     swap16(z0, z1);
@@ -360,10 +363,10 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
       const auto& Wh = uW;
       const auto& Bh = uB;
       float z[NH][4], a[NH][4];
-      z[0][0] = z0 + Bh[0][0];
-      z[0][1] = z1 + Bh[0][1];
-      z[0][2] = z2 + Bh[0][2];
-      z[0][3] = z3 + Bh[0][3];
+      z[0][0] = z0;
+      z[0][1] = z1;
+      z[0][2] = z2;
+      z[0][3] = z3;
 #pragma unroll
       for (int k = 0; k < 4; ++k) a[0][k] = act_h_t<ACT>(z[0][k]);
 #pragma unroll
@@ -443,10 +446,7 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
     {
       bool lane_need = false;  // one ballot for the four columns (no compare -> branch chain)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int ek = (int)((fbits(d[k]) >> 23) & 0xFFu);
-        lane_need |= ek > Rg[k];
-      }
+      for (int k = 0; k < 4; ++k) lane_need |= !(__builtin_fabsf(d[k]) < Tg[k]);  // (a NaN takes the rare path)
       if (__builtin_amdgcn_ballot_w64(lane_need) != 0) {
         const uint32_t e01 = wave_max_u16x2(((fbits(d[0]) >> 23) & 0xFFu) | (((fbits(d[1]) >> 23) & 0xFFu) << 16));
         const uint32_t e23 = wave_max_u16x2(((fbits(d[2]) >> 23) & 0xFFu) | (((fbits(d[3]) >> 23) & 0xFFu) << 16));
@@ -460,6 +460,7 @@ __global__ void __launch_bounds__(64 * FX_WAVES, NL == 4 ? 1 : 2)
               grow = true;
             }
             Rg[k] = Rd[k] = E[k] + 2;
+            Tg[k] = fpow2(E[k] + 3 < 255 ? E[k] + 3 : 255);  // (infinity: only an Inf / NaN delta passes it)
           }
         }
       }

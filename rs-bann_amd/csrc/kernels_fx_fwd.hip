@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(64 * FX_WAVES, 2)
     s_hw[l][r] = v;
   }
   const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 1, tp = lane & 1;
-  float zscale = st.fc[b].scale[g];
+  float zk = fx_zk(st.fc[b].scale[g]);
   v4i Areg[NU > 0 ? 8 : 1];  // the ring's W0 digit operands, one per chunk
   if constexpr (NU > 0) {
 #pragma unroll
@@ -63,8 +63,9 @@ __global__ void __launch_bounds__(64 * FX_WAVES, 2)
           *reinterpret_cast<const v4i*>(st.dig + bd.dig_off + ((int64_t)c * 64 + lane) * 16);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("" : "+v"(zscale));
+  asm volatile("" : "+v"(zk));
   __syncthreads();
+  const float zbias = s_hw[0][16 + g];  // the lane's column bias c0 (fx_z0_cum)
   v4i rowsum64 = v4i{0, 0, 0, 0};  // facc[3]'s start (field 3 stored as code - 1)
   if constexpr (NU > 0) {
 #pragma unroll
@@ -101,18 +102,17 @@ __global__ void __launch_bounds__(64 * FX_WAVES, 2)
 
   // the head of one tile: in-place fields -> z (one individual per lane) -> f
   auto head_out = [&](v4i (&facc)[4]) -> float {
-    fx_fwd_fields(facc);
-    float z0 = zscale * comb4(facc[0]), z1 = (0.25f * zscale) * comb4(facc[1]);
-    float z2 = (0.0625f * zscale) * comb4(facc[2]), z3 = (0.015625f * zscale) * comb4(facc[3]);
+    float z0, z1, z2, z3;  // with the first-layer bias
+    fx_z0_cum(facc, zk, zbias, z0, z1, z2, z3);
     swap32(z0, z2);
     swap32(z1, z3);
     swap16(z0, z1);
     swap16(z2, z3);
     float a[4];
-    a[0] = act_h_t<ACT>(z0 + uB[0][0]);
-    a[1] = act_h_t<ACT>(z1 + uB[0][1]);
-    a[2] = act_h_t<ACT>(z2 + uB[0][2]);
-    a[3] = act_h_t<ACT>(z3 + uB[0][3]);
+    a[0] = act_h_t<ACT>(z0);
+    a[1] = act_h_t<ACT>(z1);
+    a[2] = act_h_t<ACT>(z2);
+    a[3] = act_h_t<ACT>(z3);
 #pragma unroll
     for (int l = 1; l < NH; ++l) {
       float an[4];

@@ -70,12 +70,13 @@ __global__ void __launch_bounds__(64 * 8, 1)
       }
       s_hw[wave][l][rr] = v;
     }
-    float zscale = st.fc[b].scale[g];
+    float zk = fx_zk(st.fc[b].scale[g]);
     v4i Areg[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) Areg[c] = *reinterpret_cast<const v4i*>(st.dig + bd.dig_off + ((int64_t)c * 64 + lane) * 16);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (the ring is empty between passes)
-    asm volatile("" : "+v"(zscale));
+    asm volatile("" : "+v"(zk));
+    const float zbias = s_hw[wave][0][16 + g];  // the lane's column bias c0 (fx_z0_cum)
     v4i rowsum64 = v4i{0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c < 8; ++c) rowsum64 = rowsum64_acc(Areg[c], rowsum64);
@@ -105,18 +106,17 @@ __global__ void __launch_bounds__(64 * 8, 1)
       }
     };
     auto head_out = [&](v4i (&facc)[4]) -> float {
-      fx_fwd_fields(facc);
-      float z0 = zscale * comb4(facc[0]), z1 = (0.25f * zscale) * comb4(facc[1]);
-      float z2 = (0.0625f * zscale) * comb4(facc[2]), z3 = (0.015625f * zscale) * comb4(facc[3]);
+      float z0, z1, z2, z3;  // with the first-layer bias
+      fx_z0_cum(facc, zk, zbias, z0, z1, z2, z3);
       swap32(z0, z2);
       swap32(z1, z3);
       swap16(z0, z1);
       swap16(z2, z3);
       float a[4];
-      a[0] = act_h_t<ACT>(z0 + uB[0][0]);
-      a[1] = act_h_t<ACT>(z1 + uB[0][1]);
-      a[2] = act_h_t<ACT>(z2 + uB[0][2]);
-      a[3] = act_h_t<ACT>(z3 + uB[0][3]);
+      a[0] = act_h_t<ACT>(z0);
+      a[1] = act_h_t<ACT>(z1);
+      a[2] = act_h_t<ACT>(z2);
+      a[3] = act_h_t<ACT>(z3);
 #pragma unroll
       for (int l = 1; l < NH; ++l) {
         float an[4];
