@@ -90,7 +90,11 @@ const char* bann_version(void);
  * images; standardization (g - mu)/sigma with the population std
  * (bed.rs:231-242) is folded into the first-layer weights. */
 
-/* g: variant-major int8 genotypes g[j*n + i] in {0,1,2}; mu/sigma computed on device */
+/* g: variant-major int8 genotypes g[j*n + i] in {0,1,2}; mu/sigma computed on device.  The 2-bit value 3 is
+ * accepted too and counts as 3 in the statistics, the linear scores, the LD entries and on the wx and gx
+ * paths, but the tile images of the fx / fxl paths (every width <= 4, m <= 4096) cannot hold it:
+ * bann_finalize returns BANN_E_ARG when a cohort with a 3 meets a branch on one of them
+ * (bann_set_fused_enabled(0) puts every branch on gx) */
 int bann_genotypes_upload(bann_ctx* ctx, const int8_t* g, int64_t n, int64_t num_markers);
 /* payload: variant-major .bed bytes without the 3-byte signature (bed.rs:100-116),
  * ceil(n/4) bytes per marker; decoded on the device with the 2-bit LUT of
@@ -203,7 +207,8 @@ int bann_genotypes_ld_graph_pairwise(bann_ctx* ctx, int32_t window, float r2_min
  * groups may overlap.  effects [K][E], out [K][n]:
  *   out[k][i] = sum over the entries t in file order of effects[k][t] (g(i, markers[t]) - mu) / sigma
  * with the context's mu and sigma (bann_genotypes_stats, or what bann_genotypes_set_stats installed); a
- * marker with sigma = 0 contributes 0; a 2-bit field counts as its integer value 0..3, so a missing
+ * marker with sigma = 0 contributes 0; a 2-bit field counts as its integer value 0..3 (a 3 comes from
+ * bann_genotypes_upload alone; training on the fx / fxl paths refuses such a cohort), so a missing
  * call reads 0 with bann_genotypes_keep_missing on or off, as in training.  Needs a loaded cohort, no
  * branches and no bann_finalize; BANN_E_STATE after a bann_finalize that freed the image; BANN_E_ARG
  * for K outside [1, 65535], a marker index outside the cohort or offsets that decrease.

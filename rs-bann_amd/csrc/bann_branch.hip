@@ -321,6 +321,12 @@ extern "C" int bann_finalize(bann_ctx* ctx, int32_t free_raw) {
   const LayoutTotals t =
       plan_layout(ctx->n, ctx->M, cus, gx_scratch_budget(ctx->opt), ctx->fused_enabled, ctx->opt, ctx->br);
   if (t.err) return fail(ctx, t.err, t.msg);
+  if (ctx->has_code3)  // field 3 of an fx / fxl / fxh tile image holds code - 1 in two bits (fx_tile.h)
+    for (const BranchHost& h : ctx->br)
+      if (h.dev.fused == PATH_FX || h.dev.fused == PATH_FXL)
+        return fail(ctx, BANN_E_ARG,
+                    "the cohort holds the genotype value 3, which the fx / fxl kernels (widths <= 4, m <= 4096) "
+                    "cannot represent: upload values 0..2, or turn the fused kernels off");
   ctx->nfrag = t.nfrag;
   ctx->max_splits = t.max_splits;
   ctx->solo_threshold = t.solo_threshold;

@@ -16,6 +16,7 @@ int alloc_genotypes(bann_ctx* ctx, int64_t n, int64_t M) {
   CK(hipSetDevice(ctx->device));
   genotypes_release(ctx);
   ctx->missing_total = 0;
+  ctx->has_code3 = false;
   ctx->n = n;
   ctx->M = M;
   ctx->rowb = (n + 63) / 64 * 16;
@@ -109,7 +110,8 @@ extern "C" int bann_genotypes_upload(bann_ctx* ctx, const int8_t* g, int64_t n, 
   CK(hipStreamSynchronize(ctx->stream));
   dfree(d_st);
   dfree(d_flag);
-  if (flag) return fail(ctx, BANN_E_ARG, "genotypes must be 2-bit codes in 0..3 (.bed semantics)");
+  if (flag & 1) return fail(ctx, BANN_E_ARG, "genotypes must be 2-bit codes in 0..3 (.bed semantics)");
+  ctx->has_code3 = (flag & 2) != 0;
   return BANN_OK;
 }
 

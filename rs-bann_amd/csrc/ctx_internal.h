@@ -77,6 +77,9 @@ struct bann_ctx {
   bool keep_missing = false;
   uint8_t* d_pm = nullptr;
   int64_t missing_total = 0;
+  // the cohort holds the 2-bit value 3 (bann_genotypes_upload alone can load one): the fx / fxl / fxh tile
+  // images cannot store it in field 3, so bann_finalize refuses it for a branch on those paths
+  bool has_code3 = false;
   float* d_mu = nullptr;
   float* d_sigma = nullptr;
   // branches

@@ -92,8 +92,8 @@ void launch_synthetic_genotypes(uint8_t* raw, int64_t rowb, float* mu, float* si
 }
 
 // ---------------------------------------------------------------------------
-// int8 genotypes [m][n] (a staging block of markers) -> raw rows; flag |= any
-// value outside 0..3
+// int8 genotypes [m][n] (a staging block of markers) -> raw rows; flag |= 1 for any
+// value outside 0..3, |= 2 for any value 3
 // ---------------------------------------------------------------------------
 __global__ void k_i8_to_raw(const int8_t* __restrict__ g, int64_t n, int64_t m, uint8_t* __restrict__ raw,
                             int64_t rowb, int32_t* __restrict__ flag) {
@@ -107,13 +107,14 @@ __global__ void k_i8_to_raw(const int8_t* __restrict__ g, int64_t n, int64_t m, 
       const int64_t i = 4 * q + p;
       if (i < n) {
         const uint32_t v = (uint32_t)(uint8_t)g[j * n + i];
-        bad |= v > 3u;
+        bad |= (v > 3u ? 1 : 0) | (v == 3u ? 2 : 0);
         byte |= (v & 3u) << (2 * p);
       }
     }
     raw[t] = (uint8_t)byte;
   }
-  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+  if (__any(bad & 1) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+  if (__any(bad & 2) && (threadIdx.x & 63) == 0) atomicOr(flag, 2);
 }
 
 void launch_i8_to_raw(const int8_t* g, int64_t n, int64_t m, uint8_t* raw, int64_t rowb, int32_t* flag,

@@ -290,6 +290,41 @@ int main() {
     std::fprintf(stderr, "flips: %s plans as %s\n", f[0], f[1]);
     ++failures;
   }
+  // the premise of tests/test_fxl_items_gpu.py, which cannot see a split count: 64 same-shape fxl
+  // branches at n = 3000 (47 tiles), never re-split (BANN_SOLO=0), make items of at least 5 tiles --
+  // more than fxh's FXH_NSL slots, so its slot refill runs -- with or without the head-wave kernel
+  // (the split count of an fxl group does not depend on fxl_head), while one such branch alone gets
+  // one tile per item.  Not printed: the golden file keeps its cases
+  g_case = "long_items";
+  {
+    struct Row {
+      int32_t m, nsplits;
+    };
+    const Row rows[] = {{577, 8}, {1100, 4}, {2048, 4}, {2100, 4}};
+    const int64_t n = 3000, ntile = 47;
+    EnvOptions opt;
+    opt.solo = false;
+    for (const Row& r : rows)
+      for (int head : {1, 0})
+        for (int32_t layers : {2, 3, 4}) {
+          std::vector<int32_t> widths((size_t)layers, 4);
+          widths.back() = 1;
+          opt.fxl_head = head != 0;
+          std::vector<BranchHost> br = branches(std::vector<Shape>(64, Shape{r.m, widths, RA}));
+          const LayoutTotals t = plan_layout(n, 1 << 20, 256, kBudget, true, opt, br);
+          EXPECT(t.err == BANN_OK && t.solo_threshold == 0);
+          EXPECT((t.nfrag + BANN_TILE_FRAGS - 1) / BANN_TILE_FRAGS == ntile);
+          for (const BranchHost& h : br) {
+            EXPECT(h.dev.fused == PATH_FXL && h.dev.nchunks == (r.m + 63) / 64);
+            EXPECT(h.dev.nsplits == r.nsplits);
+            for (int64_t s = 0; s < h.dev.nsplits; ++s)
+              EXPECT(ntile * (s + 1) / h.dev.nsplits - ntile * s / h.dev.nsplits > FXH_NSL);
+          }
+          std::vector<BranchHost> one = branches({Shape{r.m, widths, RA}});
+          const LayoutTotals t1 = plan_layout(n, 1 << 20, 256, kBudget, true, opt, one);
+          EXPECT(t1.err == BANN_OK && one[0].dev.fused == PATH_FXL && one[0].dev.nsplits == ntile);
+        }
+  }
   // the (R, k) of the network forward's group sums: an item never spans more than tmax tiles
   g_case = "gsum";
   const int64_t tmax = 100, slots = 256;

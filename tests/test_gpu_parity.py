@@ -1242,9 +1242,15 @@ def test_fxh_head_wave_kernel(Ctx):
     """k_fused_grad_fxh (fxl shapes of 17..32 chunks: one head wave, compute waves
     of <= 5 chunks, two-tile software pipeline): oracle gradients, rss and
     predictions for ragged chunk partitions (18, 21, 27 and 32 chunks over 4..7
-    compute waves; 2, 3 and 4 layers), in solo plans (one or two tiles per item:
-    the pipeline's prologue / epilogue) and in long items (BANN_SOLO=0), packed
-    and one branch at a time; and fxl (BANN_FXL_HEAD=0) agrees to f32 rounding."""
+    compute waves; 2, 3 and 4 layers), packed and one branch at a time, with and
+    without BANN_SOLO=0; and fxl (BANN_FXL_HEAD=0) agrees to f32 rounding.
+    Every work item here is ONE tile: each branch is alone in its fxl group, so
+    best_splits gives it 47 splits for n = 3000's 47 tiles, and a solo plan as
+    many (tests/finalize_layout_check.cpp pins the one-branch count).  That is
+    the pipeline's prologue and epilogue only; its steady state, the slot refill
+    (five tiles and more) and the scale carried from tile to tile run in
+    tests/test_fxl_items_gpu.py, whose 64-branch contexts have items of 5 to 12
+    tiles."""
     rng = np.random.default_rng(41)
     n = 3000
     shapes = [(1100, [4, 4, 1], "tanh"), (1300, [3, 2, 1], "relu"), (1700, [4, 4, 4, 1], "silu"),
