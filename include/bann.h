@@ -258,6 +258,35 @@ int bann_genotypes_synthetic_maf(bann_ctx* ctx, int64_t n, int64_t num_markers, 
  * resident image. */
 int bann_genotypes_save_bed(bann_ctx* ctx, const char* stem);
 
+/* ---------------- subsets of the resident cohort: keep, extract, split, resample ----------------
+ * Replaces the PLINK run of scripts/split_train_test.sh (plink --keep .. --make-bed): dst receives the
+ * cohort of individuals[0..n_keep) x markers[0..m_keep) of src, field (j', i') of its 2-bit image =
+ * field (markers[j'], individuals[i']) of src's, gathered on the device (kernels_subset.hip); the images
+ * never leave device memory.  A NULL list stands for everyone / every marker in order (its count is
+ * ignored) and costs no index upload; both NULL is a copy.  The lists may be in any order and may
+ * repeat (bootstrap replicates, K-fold).  dst != src, both on one device, dst not finalized
+ * (BANN_E_STATE); the cohort dst holds is released, as by every loader.  src needs its image resident
+ * (BANN_E_STATE after bann_finalize(free_raw != 0)), may be finalized, and is only read.  An entry
+ * outside [0, n) or [0, M) is BANN_E_SHAPE, a non-NULL list with a count <= 0 BANN_E_ARG, both before
+ * anything is allocated or released.  dst takes over src's bann_genotypes_keep_missing setting and,
+ * where src has one, gets a presence image by the same gather; a subset without a missing call keeps
+ * none (bann_genotypes_missing_counts gives zeros).  mu and sigma of dst are recomputed from its image,
+ * as BedVM::from_file would from PLINK's output; bann_genotypes_set_stats installs the source's instead.
+ * A field value 3 (bann_genotypes_upload) is carried over, and dst refuses the fx / fxl paths only if
+ * one of its own fields holds a 3.  The work runs on dst's stream after everything src's stream has
+ * been given, and has finished when the call returns. */
+int bann_genotypes_subset(bann_ctx* dst, bann_ctx* src, const int64_t* individuals, int64_t n_keep,
+                          const int64_t* markers, int64_t m_keep);
+/* HIP-event milliseconds of the gather launches (both lists NULL: of the copies) of the last
+ * bann_genotypes_subset into ctx */
+int bann_genotypes_subset_timing(const bann_ctx* ctx, double* kernel_ms);
+/* plink --fill-missing-a2 --make-bed (scripts/fill_missing_a2.sh): the image stores a missing call as
+ * 0, the homozygous-A2 value of bed_lookup_tables.rs:4, so filling drops the presence image: the
+ * genotype image and its statistics stay as they are, bann_genotypes_missing_counts gives zeros and
+ * bann_genotypes_save_bed writes 11 where it wrote 01.  BANN_OK and nothing done with keep off or
+ * without a missing call; BANN_E_STATE when no cohort is loaded. */
+int bann_genotypes_fill_missing_a2(bann_ctx* ctx);
+
 /* ---------------- files on either side of the path (host only, no device) ---------------- */
 /* BedDims (io/dims.rs:15-34): stem.dims "n M", else the .fam / .bim line counts */
 int bann_bed_dims(const char* stem, int64_t* n_out, int64_t* num_markers_out);

@@ -122,6 +122,10 @@ SIGNATURES = {
                                          _pf32, _pf64]),
     "bann_genotypes_synthetic_maf": (C.c_int, [_P, _i64, _i64, _pf32, _u64]),
     "bann_genotypes_save_bed": (C.c_int, [_P, C.c_char_p]),
+    # subsets of the resident cohort (keep / extract / split / resample), fill-missing-a2
+    "bann_genotypes_subset": (C.c_int, [_P, _P, C.POINTER(_i64), _i64, C.POINTER(_i64), _i64]),
+    "bann_genotypes_subset_timing": (C.c_int, [_P, _pf64]),
+    "bann_genotypes_fill_missing_a2": (C.c_int, [_P]),
     "bann_io_last_error": (C.c_char_p, []),
     "bann_bim_read": (C.c_int, [C.c_char_p, C.POINTER(_i64), _pi32, C.POINTER(_i64)]),
     "bann_ld_graph_read_plink": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_i64), C.POINTER(_i64),

@@ -33,6 +33,7 @@ class BannContext:
         if rc != 0:
             raise BannError(rc, f"bann_ctx_create(device={device}) failed (no HIP device?)")
         self._h = h
+        self._device = int(device)
         self.n = 0
         self.num_markers = 0
         self._branches = []
@@ -128,6 +129,42 @@ class BannContext:
         out = np.zeros(max(int(count), 0), np.int32)
         self._check(self._lib.bann_genotypes_missing_counts(self._h, int(first), int(count), _ptr(out, C.c_int32)))
         return out
+
+    def subset(self, individuals=None, markers=None, device: Optional[int] = None) -> "BannContext":
+        """a new context holding the cohort individuals x markers of this one, gathered on the device from
+        the resident 2-bit image (plink --keep / --extract --make-bed, scripts/split_train_test.sh).  None:
+        everyone / every marker in order.  The lists may reorder and repeat (bootstrap, K-fold).  The new
+        context takes over the keep_missing setting and the missing calls, and computes its own mu / sigma.
+        device: the new context's device; it must be this context's (the default)."""
+        ind, mk = (None if a is None else np.ascontiguousarray(np.asarray(a).ravel(), dtype=np.int64)
+                   for a in (individuals, markers))
+
+        def arg(a):  # (pointer, count); an empty list keeps a real pointer, so that the library refuses it
+            if a is None:
+                return None, 0
+            return _ptr(a if a.size else np.zeros(1, np.int64), C.c_int64), a.size
+
+        out = BannContext(self._device if device is None else device)
+        try:
+            out._check(self._lib.bann_genotypes_subset(out._h, self._h, *arg(ind), *arg(mk)))
+        except Exception:
+            out.close()
+            raise
+        out.n = self.n if ind is None else ind.size
+        out.num_markers = self.num_markers if mk is None else mk.size
+        return out
+
+    def subset_timing(self) -> float:
+        """HIP-event milliseconds of the device launches of the subset() call that made this context."""
+        ms = C.c_double()
+        self._check(self._lib.bann_genotypes_subset_timing(self._h, C.byref(ms)))
+        return ms.value
+
+    def fill_missing_a2(self):
+        """plink --fill-missing-a2 (scripts/fill_missing_a2.sh): forget which calls were missing.  The image
+        already holds them as 0, the homozygous-A2 value: genotypes and statistics stay, missing_counts
+        gives zeros and save_bed writes 11 where it wrote 01."""
+        self._check(self._lib.bann_genotypes_fill_missing_a2(self._h))
 
     def download_genotypes(self, snp_idx: Sequence[int]) -> np.ndarray:
         idx = np.ascontiguousarray(snp_idx, dtype=np.int32)

@@ -11,6 +11,10 @@
   write_grouping      MarkerGrouping::to_file (group/grouping.rs:16-31)
   group_by_ld         rs-bann group-by-ld with the LD taken from the context's cohort on the device
   encode_bed_payload  int8 genotypes with -1 for a missing call -> the variant-major .bed payload
+  read_fam            the lines of a .fam, verbatim, and their count
+  split_indices / kfold_indices   ascending index lists of a train / test split and of K folds
+  split_train_test    scripts/split_train_test.sh without PLINK: one load, two device subsets, two filesets
+  fill_missing_a2     scripts/fill_missing_a2.sh without PLINK
   list_model_files / write_predictions_csv   the model listing and the CSV records of
                       rs-bann predict (rs-bann.rs:288-311); pure Python
   write_branch_r2_csv / write_population_effect_sizes_json   the outputs of rs-bann branch-r2
@@ -21,6 +25,7 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
+import shutil
 from typing import List
 
 import numpy as np
@@ -156,6 +161,82 @@ def encode_bed_payload(g) -> bytes:
     padded[:, :n] = code
     q = padded.reshape(M, -1, 4)
     return (q[:, :, 0] | (q[:, :, 1] << 2) | (q[:, :, 2] << 4) | (q[:, :, 3] << 6)).astype(np.uint8).tobytes()
+
+
+def read_fam(path: str):
+    """(lines, count) of a .fam file: one line per individual, kept verbatim (line ends included)."""
+    with open(path, "rb") as f:
+        lines = f.read().splitlines(keepends=True)
+    return lines, len(lines)
+
+
+def split_indices(n: int, test_n: int, seed: int):
+    """(train_idx, test_idx), int64 and ascending (the file order plink --keep keeps): test_n of the n
+    individuals drawn without replacement by numpy's default_rng(seed), the others train."""
+    n, test_n = int(n), int(test_n)
+    if not 0 < test_n < n:
+        raise ValueError("test_n must leave both sets non-empty: 0 < test_n < n")
+    test = np.sort(np.random.default_rng(seed).choice(n, size=test_n, replace=False)).astype(np.int64)
+    mask = np.ones(n, bool)
+    mask[test] = False
+    return np.flatnonzero(mask).astype(np.int64), test
+
+
+def kfold_indices(n: int, k: int, seed: int):
+    """k disjoint ascending int64 test lists that cover range(n), sizes within 1 of each other: a
+    default_rng(seed) permutation cut into k pieces (the train list of fold f is the others' union)."""
+    n, k = int(n), int(k)
+    if k < 2 or k > n:
+        raise ValueError("kfold_indices needs 2 <= k <= n")
+    perm = np.random.default_rng(seed).permutation(n)
+    return [np.sort(part).astype(np.int64) for part in np.array_split(perm, k)]
+
+
+def split_train_test(stem: str, test_n: int, seed: int = 0, out_train: str = None, out_test: str = None,
+                     phen: str = None, keep_missing: bool = True):
+    """scripts/split_train_test.sh without PLINK: stem.bed is loaded once, the train and the test cohort
+    are two device subsets of it, and each is written as .bed + .dims with its .fam lines (file order)
+    and a copy of the .bim; out stems default to {stem}_train / {stem}_test.  phen: a .phen of the whole
+    cohort, written as {out}.phen for each part.  keep_missing: missing calls survive as 01 (off: they
+    are written as 11, homozygous A2).  Returns (train_idx, test_idx)."""
+    from .context import BannContext
+    stem = os.fspath(stem)
+    out_train = stem + "_train" if out_train is None else os.fspath(out_train)
+    out_test = stem + "_test" if out_test is None else os.fspath(out_test)
+    fam, n = read_fam(stem + ".fam")
+    train_idx, test_idx = split_indices(n, test_n, seed)
+    y = None if phen is None else read_phen(os.fspath(phen))
+    if y is not None and y.size != n:
+        raise ValueError(f"{phen} has {y.size} phenotypes, {stem}.fam {n} individuals")
+    with BannContext(0) as src:
+        if keep_missing:
+            src.keep_missing(True)
+        src.load_bed(stem)
+        if src.n != n:
+            raise ValueError(f"{stem}: the dims announce {src.n} individuals, the .fam has {n}")
+        for out, idx in ((out_train, train_idx), (out_test, test_idx)):
+            with src.subset(individuals=idx) as part:
+                part.save_bed(out)
+            with open(out + ".fam", "wb") as f:
+                f.writelines(fam[i] for i in idx)
+            shutil.copyfile(stem + ".bim", out + ".bim")
+            if y is not None:
+                write_phen(out + ".phen", y[idx])
+    return train_idx, test_idx
+
+
+def fill_missing_a2(stem: str, out_stem: str) -> None:
+    """scripts/fill_missing_a2.sh without PLINK: stem.bed with every missing call (01) written as
+    homozygous A2 (11) into out_stem.bed + .dims, the .fam and the .bim copied."""
+    from .context import BannContext
+    stem, out_stem = os.fspath(stem), os.fspath(out_stem)
+    with BannContext(0) as ctx:
+        ctx.keep_missing(True)
+        ctx.load_bed(stem)
+        ctx.fill_missing_a2()
+        ctx.save_bed(out_stem)
+    for ext in (".fam", ".bim"):
+        shutil.copyfile(stem + ext, out_stem + ext)
 
 
 def read_phen(path: str) -> np.ndarray:

@@ -170,6 +170,111 @@ extern "C" int bann_genotypes_synthetic_maf(bann_ctx* ctx, int64_t n, int64_t nu
   return BANN_OK;
 }
 
+// a caller's index list as the device's int32 list, checked against [0, limit)
+static bool subset_list(const int64_t* idx, int64_t count, int64_t limit, std::vector<int32_t>& out) {
+  out.resize((size_t)count);
+  for (int64_t t = 0; t < count; ++t) {
+    if (idx[t] < 0 || idx[t] >= limit) return false;
+    out[(size_t)t] = (int32_t)idx[t];
+  }
+  return true;
+}
+
+// plink --keep / --extract --make-bed (scripts/split_train_test.sh) between two resident cohorts
+extern "C" int bann_genotypes_subset(bann_ctx* dst, bann_ctx* src, const int64_t* individuals, int64_t n_keep,
+                                     const int64_t* markers, int64_t m_keep) {
+  if (!dst || !src) return BANN_E_ARG;
+  bann_ctx* ctx = dst;
+  if (dst == src) return fail(ctx, BANN_E_ARG, "bann_genotypes_subset needs two contexts");
+  if (dst->device != src->device) return fail(ctx, BANN_E_ARG, "source and destination are on different devices");
+  if (dst->finalized) return fail(ctx, BANN_E_STATE, "genotypes must be set before bann_finalize");
+  if (!src->d_g) return fail(ctx, BANN_E_STATE, "the source's cohort image is not resident (no genotypes loaded, or freed at bann_finalize)");
+  if (src->n > INT32_MAX || src->M > INT32_MAX) return fail(ctx, BANN_E_SHAPE, "the source cohort exceeds 32-bit indices");
+  if ((individuals && n_keep <= 0) || (markers && m_keep <= 0)) return fail(ctx, BANN_E_ARG, "an index list needs at least one entry");
+  std::vector<int32_t> ind, mk;
+  if (individuals && !subset_list(individuals, n_keep, src->n, ind)) return fail(ctx, BANN_E_SHAPE, "individual index out of range");
+  if (markers && !subset_list(markers, m_keep, src->M, mk)) return fail(ctx, BANN_E_SHAPE, "marker index out of range");
+  const int64_t n = individuals ? n_keep : src->n, M = markers ? m_keep : src->M;
+  int rc = alloc_genotypes(dst, n, M);
+  if (rc) return rc;
+  dst->keep_missing = src->keep_missing;
+  if (src->d_pm) CK(dalloc(&dst->d_pm, dst->rowb * M));
+  dst->subset_ms = 0.0;
+  int32_t *d_ind = nullptr, *d_mk = nullptr, *d_flag = nullptr;
+  hipEvent_t ev_src = nullptr, ev0 = nullptr, ev1 = nullptr;
+  int32_t flag = 0;
+  float ms = 0.f;
+  auto run = [&]() -> hipError_t {
+    hipError_t e;
+#define SUB_TRY(call) \
+  if ((e = (call)) != hipSuccess) return e
+    // after everything the source's stream has been given
+    SUB_TRY(hipEventCreateWithFlags(&ev_src, hipEventDisableTiming));
+    SUB_TRY(hipEventRecord(ev_src, src->stream));
+    SUB_TRY(hipStreamWaitEvent(dst->stream, ev_src, 0));
+    SUB_TRY(hipEventCreate(&ev0));
+    SUB_TRY(hipEventCreate(&ev1));
+    if (individuals) {
+      SUB_TRY(dalloc(&d_ind, n));
+      SUB_TRY(hipMemcpyAsync(d_ind, ind.data(), (size_t)n * 4, hipMemcpyHostToDevice, dst->stream));
+    }
+    if (markers) {
+      SUB_TRY(dalloc(&d_mk, M));
+      SUB_TRY(hipMemcpyAsync(d_mk, mk.data(), (size_t)M * 4, hipMemcpyHostToDevice, dst->stream));
+    }
+    SUB_TRY(dalloc(&d_flag, 1));
+    SUB_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), dst->stream));
+    SUB_TRY(hipEventRecord(ev0, dst->stream));
+    if (!individuals && !markers) {  // a copy: the same rows, the same rowb
+      SUB_TRY(hipMemcpyAsync(dst->d_g, src->d_g, (size_t)(dst->rowb * M), hipMemcpyDeviceToDevice, dst->stream));
+      if (dst->d_pm)
+        SUB_TRY(hipMemcpyAsync(dst->d_pm, src->d_pm, (size_t)(dst->rowb * M), hipMemcpyDeviceToDevice, dst->stream));
+    } else {
+      launch_subset(src->d_g, src->d_pm, src->rowb, d_ind, d_mk, dst->d_g, dst->d_pm, dst->rowb, n, M, d_flag,
+                    dst->stream);
+      SUB_TRY(hipGetLastError());
+    }
+    SUB_TRY(hipEventRecord(ev1, dst->stream));
+    launch_col_stats(dst->d_g, dst->rowb, dst->d_mu, dst->d_sigma, n, M, dst->stream);
+    SUB_TRY(hipGetLastError());
+    SUB_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
+    SUB_TRY(hipStreamSynchronize(dst->stream));
+    SUB_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+#undef SUB_TRY
+    return hipSuccess;
+  };
+  const hipError_t e = run();
+  dfree(d_ind);
+  dfree(d_mk);
+  dfree(d_flag);
+  if (ev_src) (void)hipEventDestroy(ev_src);
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  CK(e);
+  dst->subset_ms = ms;
+  dst->has_code3 = (!individuals && !markers) ? src->has_code3 : flag != 0;
+  return finish_presence(dst);
+}
+
+extern "C" int bann_genotypes_subset_timing(const bann_ctx* ctx, double* kernel_ms) {
+  if (!ctx || !kernel_ms) return BANN_E_ARG;
+  *kernel_ms = ctx->subset_ms;
+  return BANN_OK;
+}
+
+// plink --fill-missing-a2 (scripts/fill_missing_a2.sh): the image already holds a missing call as 0, the
+// homozygous-A2 value, so filling is forgetting which calls were missing
+extern "C" int bann_genotypes_fill_missing_a2(bann_ctx* ctx) {
+  if (!ctx) return BANN_E_ARG;
+  if (ctx->M <= 0 || !ctx->d_mu) return fail(ctx, BANN_E_STATE, "no genotypes");
+  CK(hipSetDevice(ctx->device));
+  CK(hipStreamSynchronize(ctx->stream));
+  dfree(ctx->d_pm);
+  ctx->d_pm = nullptr;
+  ctx->missing_total = 0;
+  return BANN_OK;
+}
+
 extern "C" int bann_genotypes_stats(bann_ctx* ctx, float* mu, float* sigma) {
   if (!ctx || !ctx->d_mu) return fail(ctx, BANN_E_STATE, "no genotypes");
   if (mu) CK(hipMemcpy(mu, ctx->d_mu, ctx->M * sizeof(float), hipMemcpyDeviceToHost));

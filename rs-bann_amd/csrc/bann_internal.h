@@ -200,6 +200,16 @@ void launch_pack_tiles(const uint8_t* raw, int64_t rowb, const PackJob* jobs, in
                        int64_t ntile, uint8_t* dst, hipStream_t s);
 void launch_gather_stats(const float* mu, const float* sigma, const int32_t* snp_idx, int32_t m, float* mu_b,
                          float* sig_b, hipStream_t s);
+// subset of a cohort image (kernels_subset.hip): a lane owns SUBSET_FPL destination fields (one dword),
+// a workgroup a strip of up to SUBSET_STRIP destination individuals
+#define SUBSET_FPL 16
+#define SUBSET_STRIP 4096  // 256 lanes x SUBSET_FPL
+// dst field (r, i) = src field (mk[r], ind[i]), genotype and (src_p non-null) presence image; ind null:
+// every individual in order (rowb_dst == rowb_src), mk null: every marker in order, at least one of the
+// two given; *flag = 1 (it is never cleared) if the destination genotype image holds a field value 3
+void launch_subset(const uint8_t* src_g, const uint8_t* src_p, int64_t rowb_src, const int32_t* ind,
+                   const int32_t* mk, uint8_t* dst_g, uint8_t* dst_p, int64_t rowb_dst, int64_t n_keep, int64_t m_keep,
+                   int32_t* flag, hipStream_t s);
 
 // gx: the layered MFMA path (kernels_gx.hip)
 enum { GX_FWD0 = 0, GX_FWD = 1, GX_BWD = 2, GX_GRAD = 3, GX_GRAD0 = 4, GX_HEAD = 5 };

@@ -223,6 +223,8 @@ struct bann_ctx {
   // the HIP-event time of the device kernels of the last score or linear simulate-y call
   int64_t lin_chunk = 0;
   double lin_ms = 0.0;
+  // HIP-event time of the subset launches (or the whole-image copies) of the last bann_genotypes_subset into this context
+  double subset_ms = 0.0;
   // in-trajectory launch timing (bann_set_launch_timing): HIP events around every
   // gradient and update launch of the leapfrog sessions, resolved at bann_leapfrog_end
   bool tm_on = false;
