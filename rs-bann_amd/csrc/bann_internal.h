@@ -45,7 +45,8 @@ struct BranchDev {
   int32_t win[BANN_MAXL];     // in width of each layer (win[0] = m)
   int32_t woff[BANN_MAXL];    // param_vec offset of W_l
   int32_t boff[BANN_MAXL];    // param_vec offset of b_l (l < L-1)
-  // gx path scratch (kernels_gx.hip), float offsets from scr_off, every one a multiple of 4
+  // gx path scratch (laid out by layout_gx_scratch, finalize_layout.h; written by k_gx_prep, the GEMM epilogues of
+  // gx_tile.h and k_gx_head), float offsets from scr_off, every one a multiple of 4
   int32_t gx_w[BANN_MAXL];    // Wp_l: W_l as [out][gx_wld[l]] rows (layer 0: W0 / sigma)
   int32_t gx_wld[BANN_MAXL];  //   its row stride: win_l rounded up to 4
   int32_t gx_b[BANN_MAXL];    // b_l (layer 0: c0 = b0 - mu^T W0 / sigma), l < L-1
@@ -211,16 +212,19 @@ void launch_subset(const uint8_t* src_g, const uint8_t* src_p, int64_t rowb_src,
                    const int32_t* mk, uint8_t* dst_g, uint8_t* dst_p, int64_t rowb_dst, int64_t n_keep, int64_t m_keep,
                    int32_t* flag, hipStream_t s);
 
-// gx: the layered MFMA path (kernels_gx.hip)
+// gx: the layered MFMA path (described in kernels_gx.hip)
 enum { GX_FWD0 = 0, GX_FWD = 1, GX_BWD = 2, GX_GRAD = 3, GX_GRAD0 = 4, GX_HEAD = 5 };
 // exact (EnvOptions::gx_exact): every phase on the exact-f32 MFMA path with 64 x 64 tiles and the eager
 // head; else the bf16-plane kernels, their tile shapes and the lazy head.  One value for gx_tiles' counts
-// and every launch over them
-int64_t gx_tiles(const BranchDev& d, int ph, int l, int32_t nfrag, bool exact);
-void launch_gx_prep(const DevState& st, const int32_t* blist, int nb, hipStream_t s);
+// (gx_shapes.h) and every launch over them
+void launch_gx_prep(const DevState& st, const int32_t* blist, int nb, hipStream_t s);  // kernels_gx_head.hip
 void launch_gx_head(const DevState& st, const int32_t* blist, int nb, int max_splits, bool exact, hipStream_t s);
 void launch_gx_gemm(const DevState& st, int ph, int l, const int32_t* blist, const int32_t* prefix, int nb,
                     int total, bool exact, hipStream_t s);
+// the bf16-plane kernel of FWD0 / GRAD0 (kernels_gx_b3.hip) when not exact; launch_gx_gemm hands them on with
+// its grid of 8 per workgroups
+void launch_gx_gemm_b3(const DevState& st, int ph, const int32_t* blist, const int32_t* prefix, int nb, int total,
+                       int per, hipStream_t s);
 #define GX_HEAD_MAXW 4096   // widest summary layer of a gx branch
 void launch_fold_solo(const DevState& st, const FoldJob* jobs, int32_t njobs, int32_t max_p, hipStream_t s);
 void launch_update(const DevState& st, const int32_t* branches, int32_t nb, int32_t mode, int32_t step,

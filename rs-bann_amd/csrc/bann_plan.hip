@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "ctx_internal.h"
+#include "gx_shapes.h"
 
 // a per-call plan's scratch (bann_finalize): the gx branch list and tile prefix arrays, and
 // the branch lists, fold jobs and work items in one device block, filled by ONE copy from a

@@ -43,6 +43,7 @@
 // hidden GEMMs on the bf16 MFMA at f32 accuracy (three planes per operand).
 #include "activations.h"
 #include "bann_internal.h"
+#include "bf16_planes.h"
 #include "kernel_util.h"
 
 #define WX_WAVES 2     // waves per workgroup (the two halves of a tile)
@@ -55,8 +56,6 @@
 
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -501,7 +500,7 @@ __global__ void __launch_bounds__(64 * WX_WAVES, 2)
 // k_fused_grad_wx3 (default wide kernel): the same six phases with the three
 // hidden GEMMs (Z1, err0, dW1) on v_mfma_f32_16x16x32_bf16 at f32 accuracy.
 // Both f32 operands are split into three bf16 planes by truncation (x = x0 + x1
-// + x2 exactly, 24 significant bits; kernels_gx.hip split3) and the six plane
+// + x2 exactly, 24 significant bits; as split3 of bf16_planes.h) and the six plane
 // products of weight >= 2^-16 are accumulated in f32:
 //   a b = a0 b0 + (a0 b1 + a1 b0) + (a0 b2 + a1 b1 + a2 b0) + O(2^-24 |a b|),
 // so a 32-deep K step is 6 bf16 MFMAs (96 cycles) instead of 8 f32 16x16x4
@@ -525,9 +524,6 @@ __global__ void __launch_bounds__(64 * WX_WAVES, 2)
 #define WX3_PLANE (64 * 32)       // bytes of one (half, plane): 64 rows x 16 bf16
 #define WX3_HALF (3 * WX3_PLANE)  // one half of a plane image (6 KiB)
 #define WX3_IMG (2 * WX3_HALF)    // one plane image (12 KiB)
-
-typedef short v4s_wx __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s_wx lds_v4s_wx;
 
 namespace {
 // x = x0 + x1 + x2 by truncation (each plane the high half of an f32 word) for
@@ -576,15 +572,6 @@ __device__ __forceinline__ v4f mm6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], v
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
   return acc;
-}
-// transposing read of 8 rows (two ds_read_b64_tr_b16): lane 4 uq + up of a
-// 16-lane group addresses row uq, columns 4 up .. 4 up + 3; lane li receives
-// column li of rows 0..3 (p0) and 4..7 (p1) as K slots 0..7
-__device__ __forceinline__ bf16x8 tr16x2(const char* p0, const char* p1) {
-  const v4s_wx a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_wx*)(p0));
-  const v4s_wx b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_wx*)(p1));
-  typedef short v8s __attribute__((ext_vector_type(8)));
-  return __builtin_bit_cast(bf16x8, v8s{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
 }
 // f64 all-reduce over the 16 lanes of a row (fixed xor order, result in every lane)
 __device__ __forceinline__ double row_sum_d(double v) {
@@ -861,7 +848,7 @@ __global__ void __launch_bounds__(64 * 2 * WX3_PAIRS, 2)
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
         const char* a = sA + h * WX3_HALF + p * WX3_PLANE + 1024 * ks + tr_off;
-        ta[p] = tr16x2(a, a + 512);
+        ta[p] = tr16_pair(a, a + 512);
       }
 #pragma unroll
       for (int sb = 0; sb < 2; ++sb) {
@@ -869,7 +856,7 @@ __global__ void __launch_bounds__(64 * 2 * WX3_PAIRS, 2)
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
           const char* d = sD + sb * WX3_HALF + p * WX3_PLANE + 1024 * ks + tr_off;
-          tdl[p] = tr16x2(d, d + 512);
+          tdl[p] = tr16_pair(d, d + 512);
         }
         dW1a[sb] = mm6(ta, tdl, dW1a[sb]);
       }

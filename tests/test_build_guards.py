@@ -58,13 +58,18 @@ def test_counted_fxl_instantiations_do_not_spill(tmp_path):
 def test_production_build_sets_no_profiling_switches():
     """the fx kernel's profiling switches (FX_STAMPS phase stamps, FX_ABL ablations;
     tools/build_ab.sh builds variant libraries with them) default to 0 in the source
-    and the product build (Makefile, __graft_entry__.build) defines none of them"""
+    and the product build (Makefile, __graft_entry__.build) defines none of them; the gx
+    kernels have no compile-time switch at all, and the Makefile no gx ablation target"""
     txt = open(SRC).read()
     for sw in ("FX_STAMPS", "FX_ABL"):
         assert f"#ifndef {sw}\n#define {sw} 0\n#endif" in txt, sw
     mk = open(os.path.join(CSRC, "Makefile")).read()
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert "-DFX_" not in mk and "-DFX_" not in entry and "BANN_ABLATE" not in mk
+    assert "-DGX_" not in mk and "-DGX_" not in entry and "ablate_gx" not in mk
+    for f in sorted(os.listdir(CSRC)):
+        if os.path.isfile(os.path.join(CSRC, f)) and not f.endswith((".o", ".so")):
+            assert "#ifndef GX_" not in open(os.path.join(CSRC, f), errors="replace").read(), f
 
 
 def test_makefile_srcs_is_the_only_source_list():

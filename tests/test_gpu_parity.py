@@ -748,8 +748,9 @@ def test_layered_scratch_groups_and_packing(Ctx):
     """gx branches of mixed shapes in several scratch groups (a 1 MiB budget puts
     every branch in its own group, so later groups overwrite the scratch of
     earlier ones): every gradient matches the oracle, equals the one-group
-    result bitwise, and is bitwise reproducible.  The lazy head (kernels_gx.hip:
-    delta_s formed while BWD_s / GRAD_s stage A_s) runs for tanh, leaky ReLU and
+    result bitwise, and is bitwise reproducible.  The lazy head (k_gx_head in
+    kernels_gx_head.hip; delta_s formed while BWD_s / GRAD_s of k_gx_gemm_x3 in
+    kernels_gx.hip stage A_s) runs for tanh, leaky ReLU and
     identity after one or two hidden layers, beside branches that keep the stored
     head (SiLU, no hidden layer) in the same group."""
     rng = np.random.default_rng(29)
